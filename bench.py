@@ -2,7 +2,14 @@
 """Benchmark of the hot path: STFT power spectrogram, n_fft=2048 hop=512 Hann,
 float32, on synthetic device-resident audio (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure alone: it sets up, preconditions and warms up, times the K steps and prints the line.
+--full adds everything else the line can carry: the CPU baseline (which also checks every frame of the GPU result), the other
+BASELINE configurations and kernels under `extra`, the host-pointer and device-list faces, and the board's power and clock under
+the headline kernel.  --dump-outputs DIR writes the headline step's result of the LAST timed step as DIR/power_spectrum.npy
+(float32 [clips; 1025; frames] of rank 0; above 60 MB a fixed, seeded sample of its clips, in ascending order), so that two
+builds can be compared output for output: the inputs are the same in every run with the same arguments.
 
 One process per GPU.  Started without RANK in the environment and with N > 1, this
 process is only a launcher: it starts N fresh rank processes (RANK / LOCAL_RANK /
@@ -16,9 +23,9 @@ efficiency computed from the per-N lines compares like with like:
           owns clips [256 r, 256 r + 256) of a 256 N clip job; no collective on the data path);
           a step = one Stft.power_spectrum pass over the rank's batch through the C ABI = ONE
           launch of stft2048_power32_kernel (asserted through the library's launch counter).
-  N = 1   `extra` carries C3 (fused mel, 128 mels), C4 (FIR 8192 taps, 8 x 60 s), C1's geometry,
+  N = 1   `extra` (--full) carries C3 (fused mel, 128 mels), C4 (FIR 8192 taps, 8 x 60 s), C1's geometry,
           Stft.transform and the one-GPU point of C5, each timed with HIP events the same way.
-  N > 1   `extra.c5_strong` is BASELINE configs[4]: 4096 clips x 30 s sharded by contiguous clip
+  N > 1   `extra.c5_strong` (--full) is BASELINE configs[4]: 4096 clips x 30 s sharded by contiguous clip
           ranges (soundml_amd.shard.clip_range; 512 clips per GPU at 8), strong scaling; its
           one-GPU point is `extra.c5_one_gpu` of the N = 1 line.  (--workload c5 makes it `value`.)
 The line also says what the ranks saw: `world_size_seen`, the backend, and the per-rank kernel
@@ -33,10 +40,10 @@ earlier, and --preroll-ms (default 500) have passed (at most 2 x --preroll-ms)
 (untimed, uncounted; reported as `config.preconditioning` and, with the W warm-up steps, as `warmup_effective`): out of an idle device the
 kernel's time is not stationary (0.51 ms for three launches, 0.61-0.64 for the next ten, the sustained 0.50 after ~40 --
 profiles/r06/step_time_transient.log), and `--steps 20 --warmup 5` would sample that hump.  `value` is the sustained rate;
-`extra.c2_burst_from_idle` is the same K / W measurement out of an idle device, in every run.
+`extra.c2_burst_from_idle` is the same K / W measurement out of an idle device, in every --full run.
 
 Rank 0 prints ONE JSON line: whole-job Mframes/s, the HBM roofline of the dominant
-kernel (HIP events on the launch stream) and, at N = 1, the CPU baseline: the
+kernel (HIP events on the launch stream) and, with --full at N = 1, the CPU baseline: the
 oracle's C restatement (float64 interior, all host cores) on the SAME C2 batch, whose
 output also checks every frame of the GPU result.
 """
@@ -59,6 +66,7 @@ FIR_BYTES_PER_SAMPLE = 8                       # 4 in + 4 out
 HBM_PEAK_GBS = 8000.0                          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_MEASURED_GBS = 6290.0                      # MI355X_MICROARCH.md: what a float4 copy reaches (79 % of the spec)
 MFMA_F32_PEAK_TFLOPS = 157.3                   # MI355X_MICROARCH.md: v_mfma_f32_*_f32
+DUMP_BYTES = 60 * 10 ** 6                      # --dump-outputs: at most this many bytes of results
 
 
 def parse_args():
@@ -75,8 +83,13 @@ def parse_args():
     ap.add_argument("--clips", type=int, default=0,
                     help="override the clip count (C2: per GPU, default 256; C5: whole job, default 4096)")
     ap.add_argument("--seconds", type=float, default=0.0, help="override the clip length (C2: 10 s, C5: 30 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, every `extra` and the board's power under the kernel (each takes runs of its own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the `extra` measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/power_spectrum.npy (float32; a fixed, seeded sample of "
+                         "clips above %d MB)" % (DUMP_BYTES // 10 ** 6))
     ap.add_argument("--dry-run", action="store_true",
                     help="rank plumbing only (no GPU, no library): rendezvous over gloo, barrier, MAX-reduce, one JSON line")
     ap.add_argument("--verify-shards", action="store_true",
@@ -201,6 +214,24 @@ def cpu_baseline(x_host, gpu_out_host):
                             "cpu_us_per_frame_one_thread": round(cpu_dt1 / (k1 * O.frames(c, n)) * 1e6, 2)},
             "gpu_vs_oracle_max_err_over_peak": float("%.3g" % worst), "gpu_vs_oracle_frames_checked": frames,
             "gate": 1e-5}
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the result of the timed path's last step, [clips; bins; frames] float32, as path/power_spectrum.npy.
+    Above DUMP_BYTES a fixed sample: clips drawn by a generator seeded 0, in ascending order (and, should one clip alone exceed
+    the budget, its leading frames)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    clips, bins, frames = out.shape
+    per_clip = bins * frames * 4
+    if clips * per_clip > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // max(per_clip, 1))
+        idx = torch.tensor(sorted(np.random.default_rng(0).choice(clips, size=keep, replace=False).tolist()), device=out.device)
+        out = out.index_select(0, idx)
+        if per_clip > DUMP_BYTES:
+            out = out[:, :, :max(1, DUMP_BYTES // (bins * 4))]
+    np.save(os.path.join(path, "power_spectrum.npy"), np.ascontiguousarray(out.cpu().numpy(), dtype=np.float32))
 
 
 def workload_name(workload, clips_arg, seconds_arg, world):
@@ -357,6 +388,8 @@ def main():
     elapsed, step_ms, launches = timed(power_step(x, out, clips, n, frames), args.steps, args.warmup)
     main_preroll_steps = timed.preroll_steps
     main_settled = timed.settled
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # One step is ONE launch of the fused kernel (interior tiles, then the few border frames of every clip through
     # the same frame code), so the HIP events around a step are that kernel's launch durations: their average is
     # what `rocprofv3 --kernel-trace --stats` of this command reports for it (profiles/).
@@ -439,11 +472,11 @@ def main():
             line["shard_check"] = shard_check
 
     # ---- CPU baseline on the same batch (rank 0, one GPU) ------------------------------------------------------
-    if world == 1 and workload == "c2" and not args.no_cpu_baseline:
+    if args.full and world == 1 and workload == "c2" and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(x.cpu().numpy(), out.cpu().numpy())
 
     # ---- extras: the other BASELINE configurations, same HIP-event method ---------------------------------------
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         k, w = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
         if world == 1 and workload == "c2" and clips == 256:
             # The headline measurement WITHOUT its preconditioning: W warm-up steps and K timed ones right out of an idle device
@@ -691,7 +724,7 @@ def main():
     # device list the C ABI cuts `lead` into contiguous clip ranges, one host thread + staging ring pair + PCIe link per device, every
     # range writing its slice of the one result.  C5-shaped: 32 clips x 30 s per listed device, PCIe inclusive,
     # a fresh result per call (from the page-locked pool).  N > 1: rank 0 drives all N devices while the other ranks wait at a barrier.
-    if not args.no_extras and workload == "c2" and not args.clips:
+    if args.full and not args.no_extras and workload == "c2" and not args.clips:
         barrier()
         if rank == 0:
             try:   # (an extra: a failure on a device set this code has never met must not take the headline line with it -- it is reported in the row)
@@ -759,7 +792,7 @@ def main():
     # rocm-smi is a `#!/usr/bin/env python3` script: it is started with the profiler's variables scrubbed (under rocprofv3 this
     # process carries LD_PRELOAD / ROCP_* / HSA_TOOLS_*, and a child that inherits them would be an exec hop with the profiler's library
     # loaded), and not at all when a counter collection is active.
-    if world == 1 and workload == "c2" and rank == 0:
+    if args.full and world == 1 and workload == "c2" and rank == 0:
         def power_sample():
             import subprocess, threading
             if os.environ.get("ROCPROF_COUNTER_COLLECTION") or os.environ.get("ROCPROF_PMC"):   # (rocprofv3 --pmc: no child processes at all)

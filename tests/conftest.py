@@ -1,3 +1,4 @@
+import hashlib
 import json
 import os
 import sys
@@ -25,6 +26,21 @@ def load_golden(suite, name):
 
 def golden_cases(suite, name):
     return [pytest.param(c, id=c["name"]) for c in load_golden(suite, name)["cases"]]
+
+
+def shape_digest(*arrays):
+    """SHA-256 of complex128 arrays' bytes with -0.0 made +0.0: equal digests <=> np.array_equal (no NaNs).
+    tests/golden/resample/ref_shape_digests.json holds the reference's resample shaping outputs in this form."""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update((np.ascontiguousarray(a, dtype=np.complex128) + 0.0).tobytes())
+    return h.hexdigest()
+
+
+def ref_shape_digests(suite, l, m):
+    """(input digest, output digest) of the reference's `soundml_resample_shape_run` for one case of `suite` ("cpu" or "gpu")"""
+    row = load_golden("resample", "ref_shape_digests")[suite]["%d-%d" % (l, m)]
+    return row["input"], row["output"]
 
 
 # reference tolerances: test/support/tutils.ml:80-86, stft_goldens.ml:13-17

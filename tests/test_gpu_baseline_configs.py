@@ -182,6 +182,33 @@ def test_bench_two_ranks_one_box():
     assert line["value"] > 0
 
 
+@pytest.mark.timeout(900)
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run measures the headline alone and --dump-outputs writes its last step's result: here 20 clips x 10 s
+    (77 MB of spectrogram) -> the seeded sample of 15 clips, equal bit for bit to Stft.power_spectrum of the same clips.  --full
+    still adds the CPU baseline, which checks every frame of the GPU result."""
+    import torch
+    def bench(clips, seconds, *more):
+        return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--clips", str(clips), "--seconds",
+                               str(seconds), "--steps", "3", "--warmup", "1", "--preroll-ms", "0"] + list(more),
+                              capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = bench(20, 10, "--dump-outputs", str(tmp_path))
+    assert out.returncode == 0, out.stdout + out.stderr
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f32"
+    assert "extra" not in line and "cpu_baseline" not in line and "board_under_the_kernel" not in line["roofline"]
+    got = np.load(str(tmp_path / "power_spectrum.npy"))
+    pick = sorted(np.random.default_rng(0).choice(20, size=15, replace=False).tolist())
+    assert got.dtype == np.float32 and got.shape == (15, 1025, 938) and got.nbytes <= 64 * 10 ** 6
+    x = clip_batch(torch, 0, 20, 480000)[torch.tensor(pick, device="cuda")]
+    assert np.array_equal(got, Stft.power_spectrum(Stft.Config.create(fft_size=2048, hop=512), x).cpu().numpy())
+    full = bench(8, 3, "--full", "--no-extras")
+    assert full.returncode == 0, full.stdout + full.stderr
+    fl = json.loads(full.stdout.strip().splitlines()[-1])
+    assert fl["cpu_baseline"]["gpu_vs_oracle_max_err_over_peak"] <= CONTRACT
+    assert fl["cpu_baseline"]["gpu_vs_oracle_frames_checked"] == 8 * 282
+
+
 @pytest.mark.parametrize("fft,hop", [(1024, 256), (512, 128), (2048, 512)])
 def test_regression_gate_fast_kernels(fft, hop):
     """the float32 kernels of the three common sizes at 2e-6 of the peak (power and complex faces)"""

@@ -15,7 +15,8 @@ import os
 import numpy as np
 import pytest
 
-from conftest import (F32_ATOL, F32_RTOL, F64_ATOL, F64_RTOL, ROOT, check_close, load_golden)
+from conftest import (F32_ATOL, F32_RTOL, F64_ATOL, F64_RTOL, ROOT, check_close, load_golden, ref_shape_digests,
+                      shape_digest)
 from oracle import soundml_oracle as O
 
 # every synthesis vector file of the reference (soundml/test/istft/vectors; Griffin-Lim files apart)
@@ -1394,10 +1395,11 @@ def test_resample_shape_is_the_reference_stub_bit_for_bit(l, m):
     got = Resample.shape(spec, oh, n, l, m)
     assert np.array_equal(got, c_oracle.resample_shape(spec, oh, n, l, m))
     assert np.array_equal(got, O.ols_shape(spec, oh, n, l, m))
-    # the reference's own compiled `soundml_resample_shape_run` (oracle/_ref: built from the reference's source where it lies,
-    # the .so travels to the GPU box) is the checker proper
-    assert c_oracle.have_ref()
-    assert np.array_equal(got, c_oracle.ref_resample_shape(spec, oh, n, l, m))
+    # the reference's own compiled `soundml_resample_shape_run` is the checker proper: its outputs on these inputs, pinned as
+    # digests (tests/golden/resample/ref_shape_digests.json, tools/gen_ref_shape_digests.py)
+    want_in, want_out = ref_shape_digests("gpu", l, m)
+    assert shape_digest(spec, oh) == want_in, "inputs differ from those the reference's digests were taken on"
+    assert shape_digest(got) == want_out
     assert np.array_equal(Resample.shape(spec[3:4], oh, n, l, m), got[3:4])
 
 

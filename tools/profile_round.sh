@@ -13,11 +13,11 @@ cd /tmp && export TMPDIR=/tmp
 # headline kernel, <true, 2, false, 2>, so it does not pollute the average of C2's <true, 2, false, 1>): the line it prints and the
 # per-dispatch trace of the SAME run -- profiles/hbm_traffic.json takes every kernel's duration from this trace (median over the
 # kernel's launches in the run: preconditioning + timed steps) and holds it against the `ms` this line reports.
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --no-cpu-baseline > "$OUT/bench_n1.json" 2> "$OUT/trace.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --full --no-cpu-baseline > "$OUT/bench_n1.json" 2> "$OUT/trace.err"
 find "$OUT/trace" -name '*kernel_stats.csv' | head -1 | xargs -r -I{} cp {} "$OUT/kernel_stats.csv"
 find "$OUT/trace" -name '*kernel_trace.csv' | head -1 | xargs -r -I{} cp {} "$OUT/bench_kernel_trace.csv"
-# the plain bench line of the same box (every `extra`): what profiles/hbm_traffic.json's per-kernel durations are held against
-(cd "$ROOT" && timeout 600 python3 bench.py > "$OUT/bench_n1_full.json" 2> "$OUT/bench_full.err")
+# the --full bench line of the same box (every `extra`): what profiles/hbm_traffic.json's per-kernel durations are held against
+(cd "$ROOT" && timeout 600 python3 bench.py --full > "$OUT/bench_n1_full.json" 2> "$OUT/bench_full.err")
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_hot" -- python3 $ROOT/tools/pmc_driver.py > "$OUT/trace_hot.log" 2>&1
 find "$OUT/trace_hot" -name '*kernel_stats.csv' | head -1 | xargs -r -I{} cp {} "$OUT/hot_kernel_stats.csv"
 find "$OUT/trace_hot" -name '*kernel_trace.csv' | head -1 | xargs -r -I{} cp {} "$OUT/hot_kernel_trace.csv"
