@@ -10,6 +10,8 @@
 #include <cstring>
 #include <atomic>
 #include <condition_variable>
+#include <deque>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -47,39 +49,6 @@ void launch_stft(const StftJob &job) {
 }
 
 namespace {
-
-template <typename F>
-int guarded(F &&body) {
-  try {
-    body();
-    return SMX_OK;
-  } catch (const InvalidArgument &e) {
-    set_last_error(e.what());
-    return SMX_INVALID_ARGUMENT;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return SMX_FAILURE;
-  }
-}
-
-void require_device() {
-  int count = 0;
-  hipError_t err = hipGetDeviceCount(&count);
-  if (err != hipSuccess || count < 1)
-    throw Failure("soundml_amd: no HIP device is available (this library has no CPU fallback)");
-}
-
-struct DeviceScratch {  // RAII device allocation for the host-pointer entry points, from the stream-ordered pool:
-  void *ptr = nullptr;  // hipFree of a GB-sized array costs more than the kernels; the pool keeps it for the next call
-  explicit DeviceScratch(size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    init_device_pool();
-    SMX_HIP_CHECK(smx::pool_malloc_async(&ptr, bytes, nullptr));
-  }
-  ~DeviceScratch() { (void)hipFreeAsync(ptr, nullptr); }
-  DeviceScratch(const DeviceScratch &) = delete;
-  DeviceScratch &operator=(const DeviceScratch &) = delete;
-};
 
 // ---- the device list of the host-pointer batch calls (smx_set_devices; round 6) ----------------------------------------------
 // The reference's caller is ONE process handing over host tensors, "a batch of clips is one call" (stft.mli:211-250); its leading
@@ -122,10 +91,12 @@ void for_each_shard(int64_t lead, F &&body) {
   std::mutex gate_mutex;
   std::condition_variable gate_cv;
   int64_t arrived = 0;
+  bool abandoned = false;   // a shard's thread could not start: nobody waits for it, and no shard runs
   auto rendezvous = [&] {
     std::unique_lock<std::mutex> g(gate_mutex);
     if (++arrived == shards) gate_cv.notify_all();
-    else gate_cv.wait(g, [&] { return arrived == shards; });
+    else gate_cv.wait(g, [&] { return arrived == shards || abandoned; });
+    return !abandoned;
   };
   auto run = [&](int64_t s) {
     bool met = false;
@@ -133,30 +104,100 @@ void for_each_shard(int64_t lead, F &&body) {
       const hipError_t set = hipSetDevice(devices[(size_t)s]);
       if (set == hipSuccess) (void)hipFree(nullptr);   // (the thread's HIP state for the device exists before the rendezvous)
       met = true;
-      rendezvous();
-      SMX_HIP_CHECK(set);
-      set_transfer_share((int)shards);
-      int64_t lo, hi;
-      clip_range(lead, shards, s, lo, hi);
-      if (hi > lo) body(lo, hi - lo);
+      if (rendezvous()) {
+        SMX_HIP_CHECK(set);
+        set_transfer_share((int)shards);
+        int64_t lo, hi;
+        clip_range(lead, shards, s, lo, hi);
+        if (hi > lo) body(lo, hi - lo);
+      }
     } catch (...) {
       errors[(size_t)s] = std::current_exception();
       if (!met) rendezvous();   // (nobody waits for a shard that failed early)
     }
     set_transfer_share(1);
   };
-  if (shards == 1) {
-    run(0);
-    (void)hipSetDevice(caller_device);
-  } else {
-    std::vector<std::thread> threads;
-    for (int64_t s = 1; s < shards; ++s) threads.emplace_back(run, s);
-    run(0);   // the caller's thread takes the first shard
+  std::vector<std::thread> threads;
+  int64_t s = 1;
+  try {
+    for (; s < shards; ++s) threads.emplace_back(run, s);
+  } catch (const std::exception &e) {   // (a joinable std::thread destroyed unjoined would terminate the process)
+    {
+      std::lock_guard<std::mutex> g(gate_mutex);
+      abandoned = true;
+    }
+    gate_cv.notify_all();
     for (auto &t : threads) t.join();
     (void)hipSetDevice(caller_device);
+    throw Failure(format("soundml_amd: cannot start the host thread of shard %lld of %lld (%s)", (long long)s, (long long)shards,
+                         e.what()));
   }
+  run(0);   // the caller's thread takes the first shard
+  for (auto &t : threads) t.join();
+  (void)hipSetDevice(caller_device);
   for (auto &e : errors)
     if (e) std::rethrow_exception(e);
+}
+
+// One input array of a host-pointer call: clip_bytes per clip.  A null host pointer is an absent optional input: no device copy,
+// and the device function sees a null pointer.
+struct HostIn {
+  const void *host;
+  size_t clip_bytes;
+};
+
+// The host-pointer form of a batch call of `lead` clips whose arguments the caller has checked: require_device, then per clip range
+// device copies of the inputs and of the result, upload, dev(d_in, d_out, nclips, stream), download.  dev enqueues the work of
+// nclips clips on `stream` with d_in[i] / d_out at their first clip.
+//   shard     the device list's clip ranges side by side (for_each_shard)
+//   pipeline  (one input) a large batch is cut into units of clips whose upload, kernels and download overlap (transfer.cpp; a
+//             unit's result is the slice of the whole call's bit for bit: the reference's per-slice law, stft_grid.ml:180-205),
+//             this configuration's tables built first.  SMX_HOST_PIPELINE=0: serially.
+template <class Dev>
+void host_call(const char *name, std::initializer_list<HostIn> inputs, void *out, size_t out_clip, int64_t lead, bool shard,
+               const smx_stft_config *pipeline, Dev &&dev) {
+  require_device();
+  const std::vector<HostIn> in(inputs);
+  auto one = [&](int64_t clip0, int64_t nc) {
+    static const bool trace = env_flag("SMX_HOST_TRACE") == 1;   // diagnostic: where a host call's time goes
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    std::deque<DeviceScratch> scratch;
+    std::vector<void *> d_in;
+    for (const HostIn &i : in) d_in.push_back(i.host ? scratch.emplace_back((size_t)nc * i.clip_bytes).ptr : nullptr);
+    DeviceScratch d_out((size_t)nc * out_clip);
+    const double t1 = now();
+    void *dst = reinterpret_cast<unsigned char *>(out) + (size_t)clip0 * out_clip;
+    const size_t in_clip = in[0].clip_bytes;
+    // (without page-locked staging memory the pipelined form cannot run: the serial path's plain hipMemcpy still completes the call)
+    if (pipeline && in.size() == 1 && nc >= 8 && (size_t)nc * (in_clip + out_clip) >= ((size_t)128 << 20) && in_clip > 0 &&
+        out_clip > 0 && env_flag("SMX_HOST_PIPELINE") != 0 && staging_available()) {
+      int64_t unit = (int64_t)(((size_t)48 << 20) / std::max(in_clip, out_clip));   // ~48 MB of the larger side per unit
+      unit = std::max<int64_t>(1, std::min<int64_t>(unit, (nc + 3) / 4));
+      SMX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the scratch arrays come from the null stream's pool
+      (void)pipeline->tables();                      // (lazy tables are built before the threads start)
+      pipelined_host_call(reinterpret_cast<const unsigned char *>(in[0].host) + (size_t)clip0 * in_clip, in_clip, dst, out_clip, nc, unit,
+                          d_in[0], d_out.ptr, [&](int64_t u0, int64_t un, hipStream_t stream) {
+                            const void *d_unit = reinterpret_cast<const unsigned char *>(d_in[0]) + (size_t)u0 * in_clip;
+                            dev(&d_unit, reinterpret_cast<unsigned char *>(d_out.ptr) + (size_t)u0 * out_clip, un, stream);
+                          });
+      if (trace) fprintf(stderr, "[smx] host %s: allocate %.2f ms, pipelined upload / kernels / download %.2f (units of %lld clips)\n", name, t1 - t0, now() - t1, (long long)unit);
+      return;
+    }
+    for (size_t i = 0; i < in.size(); ++i)
+      if (in[i].host)
+        copy_to_device(d_in[i], reinterpret_cast<const unsigned char *>(in[i].host) + (size_t)clip0 * in[i].clip_bytes, (size_t)nc * in[i].clip_bytes);
+    const double t2 = now();
+    dev(d_in.data(), d_out.ptr, nc, nullptr);
+    SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
+    const double t3 = now();
+    copy_to_host(dst, d_out.ptr, (size_t)nc * out_clip);
+    if (trace)
+      fprintf(stderr, "[smx] host %s: allocate %.2f ms, upload %.2f, kernels %.2f, download %.2f\n", name, t1 - t0, t2 - t1,
+              t3 - t2, now() - t3);
+  };
+  if (shard) for_each_shard(lead, one);
+  else one(0, lead);
 }
 
 void check_config(const void *c, const char *fn) {
@@ -177,18 +218,13 @@ void check_range(const smx_stft_config &c, int64_t n, int64_t p0, int64_t p1) {
         (long long)p0, (long long)p1, (long long)total));
 }
 
-// device-resident analysis of frames [p0, p1)
-void stft_range_dev(const smx_stft_config &c, const void *d_x, int in_bytes, int64_t lead, int64_t n,
-                    int64_t x_stride, int64_t p0, int64_t p1, OutMode mode, double power, void *d_out,
-                    hipStream_t stream) {
-  check_rank_extents("transform_range", lead, n);
-  if (x_stride < n) throw Failure("transform_range: x_stride is smaller than the signal length");
-  check_range(c, n, p0, p1);
-  if (p0 == p1 || lead == 0) return;  // frameless_spectrum: nothing to write (stft.ml:629-630)
-  if (!d_x || !d_out) throw Failure("transform_range: null device pointer");
+// the analysis of frames [p0, p0 + count) of x by c into out, dense ([lead; bins; count]); float64 audio has the float64 interior,
+// float32 audio the library's (smx_set_interior)
+StftJob stft_job(const smx_stft_config &c, const void *x, int in_bytes, int64_t lead, int64_t n, int64_t x_stride, int64_t p0,
+                 int64_t count, OutMode mode, double power, void *out, hipStream_t stream) {
   StftJob job;
   job.cfg = &c;
-  job.x = d_x;
+  job.x = x;
   job.in_bytes = in_bytes;
   job.interior = in_bytes == 8 ? SMX_INTERIOR_F64 : g_interior.load();
   job.lead = lead;
@@ -198,75 +234,39 @@ void stft_range_dev(const smx_stft_config &c, const void *d_x, int in_bytes, int
   job.pad = c.pad;
   job.pad_value = c.pad_value;
   job.p0 = p0;
-  job.count = p1 - p0;
+  job.count = count;
   job.mode = mode;
   job.power = power;
-  job.out = d_out;
-  job.out_stride = p1 - p0;
-  job.out_offset = 0;
+  job.out = out;
+  job.out_stride = count;
   job.stream = stream;
-  launch_stft(job);
+  return job;
 }
 
-// host-pointer analysis on the current device: upload, run, download
-void stft_range_host_one(const smx_stft_config &c, const void *x, int in_bytes, int64_t lead, int64_t n,
-                         int64_t p0, int64_t p1, OutMode mode, double power, void *out) {
-  check_rank_extents("transform", lead, n);
+// device-resident analysis of frames [p0, p1)
+void stft_range_dev(const smx_stft_config &c, const void *d_x, int in_bytes, int64_t lead, int64_t n,
+                    int64_t x_stride, int64_t p0, int64_t p1, OutMode mode, double power, void *d_out,
+                    hipStream_t stream) {
+  check_rank_extents("transform_range", lead, n);
+  if (x_stride < n) throw Failure("transform_range: x_stride is smaller than the signal length");
   check_range(c, n, p0, p1);
-  const int64_t count = p1 - p0;
-  const size_t out_elems = (size_t)lead * (size_t)c.bins() * (size_t)count * (mode == OUT_COMPLEX ? 2 : 1);
-  if (count == 0 || lead == 0) return;
-  if (!x || !out) throw Failure("transform: null pointer");
-  require_device();
-  static const bool trace = env_flag("SMX_HOST_TRACE") == 1;   // diagnostic: where a host call's time goes
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  DeviceScratch dx((size_t)lead * (size_t)n * (size_t)in_bytes);
-  DeviceScratch dout(out_elems * (size_t)in_bytes);
-  const double t1 = now();
-  // A large batch is cut into units of clips whose upload, kernels and download overlap (transfer.cpp; a unit's result is the
-  // slice of the whole call's bit for bit: the reference's per-slice law, stft_grid.ml:180-205).  SMX_HOST_PIPELINE=0: serially.
-  const size_t in_clip = (size_t)n * (size_t)in_bytes, out_clip = out_elems / (size_t)lead * (size_t)in_bytes;
-  // (without page-locked staging memory the pipelined form cannot run: the serial path's plain hipMemcpy still completes the call)
-  if (lead >= 8 && (size_t)lead * (in_clip + out_clip) >= ((size_t)128 << 20) && in_clip > 0 && env_flag("SMX_HOST_PIPELINE") != 0 &&
-      staging_available()) {
-    int64_t unit = (int64_t)(((size_t)48 << 20) / std::max(in_clip, out_clip));   // ~48 MB of the larger side per unit
-    unit = std::max<int64_t>(1, std::min<int64_t>(unit, (lead + 3) / 4));
-    SMX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the scratch arrays come from the null stream's pool
-    (void)c.tables();                              // (lazy tables are built before the threads start)
-    pipelined_host_call(x, in_clip, out, out_clip, lead, unit, dx.ptr, dout.ptr, [&](int64_t clip0, int64_t nc, hipStream_t stream) {
-      stft_range_dev(c, reinterpret_cast<const unsigned char *>(dx.ptr) + (size_t)clip0 * in_clip, in_bytes, nc, n, n, p0, p1, mode, power,
-                     reinterpret_cast<unsigned char *>(dout.ptr) + (size_t)clip0 * out_clip, stream);
-    });
-    if (trace) fprintf(stderr, "[smx] host transform: allocate %.2f ms, pipelined upload / kernels / download %.2f (units of %lld clips)\n", t1 - t0, now() - t1, (long long)unit);
-    return;
-  }
-  copy_to_device(dx.ptr, x, (size_t)lead * (size_t)n * (size_t)in_bytes);
-  const double t2 = now();
-  stft_range_dev(c, dx.ptr, in_bytes, lead, n, n, p0, p1, mode, power, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  const double t3 = now();
-  copy_to_host(out, dout.ptr, out_elems * (size_t)in_bytes);
-  if (trace)
-    fprintf(stderr, "[smx] host transform: allocate %.2f ms, upload %.2f, kernels %.2f, download %.2f\n", t1 - t0, t2 - t1,
-            t3 - t2, now() - t3);
+  if (p0 == p1 || lead == 0) return;  // frameless_spectrum: nothing to write (stft.ml:629-630)
+  if (!d_x || !d_out) throw Failure("transform_range: null device pointer");
+  launch_stft(stft_job(c, d_x, in_bytes, lead, n, x_stride, p0, p1 - p0, mode, power, d_out, stream));
 }
 
-// host-pointer analysis: the whole batch on the current device, or -- with a device list (smx_set_devices) -- contiguous clip
-// ranges on the listed devices side by side (a range's result is the slice of the whole call's bit for bit: stft_grid.ml:180-205)
+// host-pointer analysis: the current device, or the device list's clip ranges side by side; a large batch pipelined
 void stft_range_host(const smx_stft_config &c, const void *x, int in_bytes, int64_t lead, int64_t n,
                      int64_t p0, int64_t p1, OutMode mode, double power, void *out) {
   check_rank_extents("transform", lead, n);
   check_range(c, n, p0, p1);
   if (p1 == p0 || lead == 0) return;
   if (!x || !out) throw Failure("transform: null pointer");
-  require_device();
-  const size_t in_clip = (size_t)n * (size_t)in_bytes;
   const size_t out_clip = (size_t)c.bins() * (size_t)(p1 - p0) * (mode == OUT_COMPLEX ? 2 : 1) * (size_t)in_bytes;
-  for_each_shard(lead, [&](int64_t clip0, int64_t nc) {
-    stft_range_host_one(c, reinterpret_cast<const unsigned char *>(x) + (size_t)clip0 * in_clip, in_bytes, nc, n, p0, p1, mode, power,
-                        reinterpret_cast<unsigned char *>(out) + (size_t)clip0 * out_clip);
-  });
+  host_call("transform", {{x, (size_t)n * (size_t)in_bytes}}, out, out_clip, lead, true, &c,
+            [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              stft_range_dev(c, d_in[0], in_bytes, nc, n, n, p0, p1, mode, power, d_out, stream);
+            });
 }
 
 // Stft.invert's checks (stft.ml:745-786), in the reference's order and wording
@@ -310,39 +310,8 @@ void invert_dev(const smx_stft_config &c, const void *d_z, int z_bytes, int64_t 
   launch_istft(job);
 }
 
-void invert_host_one(const smx_stft_config &c, const void *z, int z_bytes, int64_t lead, int64_t bins, int64_t frames,
-                     int has_length, int64_t length, void *out) {
-  if (lead < 0 || frames < 0) throw Failure("invert: negative extent");
-  check_synthesis(c, bins, length, has_length != 0);
-  const int64_t out_len = has_length ? length : stft_output_length(c, frames);
-  if (lead == 0 || out_len == 0) return;
-  if (!out || (frames > 0 && !z)) throw Failure("invert: null pointer");
-  require_device();
-  const size_t zb = (size_t)lead * (size_t)bins * (size_t)frames * (size_t)z_bytes;
-  const size_t ob = (size_t)lead * (size_t)out_len * (size_t)(z_bytes / 2);
-  DeviceScratch dz(zb), dout(ob);
-  // a large batch in units of clips whose upload, synthesis and download overlap (as stft_range_host; every clip is synthesised
-  // on its own: stft.mli:214-218)
-  const size_t z_clip = (size_t)bins * (size_t)frames * (size_t)z_bytes, o_clip = (size_t)out_len * (size_t)(z_bytes / 2);
-  if (lead >= 8 && zb + ob >= ((size_t)128 << 20) && z_clip > 0 && o_clip > 0 && env_flag("SMX_HOST_PIPELINE") != 0 && staging_available()) {
-    int64_t unit = (int64_t)(((size_t)48 << 20) / std::max(z_clip, o_clip));
-    unit = std::max<int64_t>(1, std::min<int64_t>(unit, (lead + 3) / 4));
-    SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    (void)c.tables();
-    pipelined_host_call(z, z_clip, out, o_clip, lead, unit, dz.ptr, dout.ptr, [&](int64_t clip0, int64_t nc, hipStream_t stream) {
-      invert_dev(c, reinterpret_cast<const unsigned char *>(dz.ptr) + (size_t)clip0 * z_clip, z_bytes, nc, bins, frames, has_length, length,
-                 reinterpret_cast<unsigned char *>(dout.ptr) + (size_t)clip0 * o_clip, stream);
-    });
-    return;
-  }
-  if (zb) copy_to_device(dz.ptr, z, zb);
-  invert_dev(c, dz.ptr, z_bytes, lead, bins, frames, has_length, length, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, ob);
-}
-
 // host-pointer synthesis: the current device, or the device list's clip ranges side by side (every clip is synthesised on its
-// own: stft.mli:214-218)
+// own: stft.mli:214-218); a large batch pipelined
 void invert_host(const smx_stft_config &c, const void *z, int z_bytes, int64_t lead, int64_t bins, int64_t frames,
                  int has_length, int64_t length, void *out) {
   if (lead < 0 || frames < 0) throw Failure("invert: negative extent");
@@ -350,12 +319,10 @@ void invert_host(const smx_stft_config &c, const void *z, int z_bytes, int64_t l
   const int64_t out_len = has_length ? length : stft_output_length(c, frames);
   if (lead == 0 || out_len == 0) return;
   if (!out || (frames > 0 && !z)) throw Failure("invert: null pointer");
-  require_device();
-  const size_t z_clip = (size_t)bins * (size_t)frames * (size_t)z_bytes, o_clip = (size_t)out_len * (size_t)(z_bytes / 2);
-  for_each_shard(lead, [&](int64_t clip0, int64_t nc) {
-    invert_host_one(c, z ? reinterpret_cast<const unsigned char *>(z) + (size_t)clip0 * z_clip : nullptr, z_bytes, nc, bins, frames, has_length,
-                    length, reinterpret_cast<unsigned char *>(out) + (size_t)clip0 * o_clip);
-  });
+  host_call("invert", {{z, (size_t)bins * (size_t)frames * (size_t)z_bytes}}, out, (size_t)out_len * (size_t)(z_bytes / 2), lead, true,
+            &c, [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              invert_dev(c, d_in[0], z_bytes, nc, bins, frames, has_length, length, d_out, stream);
+            });
 }
 
 }  // namespace
@@ -442,25 +409,7 @@ int smx_debug_stft_transform_frame_major_f32_dev(const smx_stft_config *c, const
                                                  int64_t pitch_floats, int64_t rows_per_clip, void *stream) {
   return guarded([&] {
     check_config(c, "transform");
-    StftJob job;
-    job.cfg = c;
-    job.x = d_x;
-    job.in_bytes = 4;
-    job.interior = g_interior.load();
-    job.lead = lead;
-    job.n = n;
-    job.x_stride = n;
-    job.left = c->left_width();
-    job.pad = c->pad;
-    job.pad_value = c->pad_value;
-    job.p0 = 0;
-    job.count = c->frames(n);
-    job.mode = OUT_COMPLEX;
-    job.power = 0.0;
-    job.out = d_out;
-    job.out_stride = job.count;
-    job.out_offset = 0;
-    job.stream = (hipStream_t)stream;
+    const StftJob job = stft_job(*c, d_x, 4, lead, n, n, 0, c->frames(n), OUT_COMPLEX, 0.0, d_out, (hipStream_t)stream);
     if (!launch_stft_complex_fm(job, d_out, pitch_floats, rows_per_clip)) throw Failure("transform (frame-major): not eligible");
   });
 }
@@ -873,25 +822,10 @@ int64_t process(smx_stft_kernel &k, const void *extra, int64_t extra_stride, int
     SMX_HIP_CHECK(hipMalloc(&k.d_out, (size_t)k.channels * (size_t)bins * (size_t)cap * 2 * es));   // sized for either face
     k.out_cap = cap;
   }
-  StftJob job;
-  job.cfg = &c;
-  job.x = k.d_stream;
-  job.in_bytes = k.dtype_bytes;
-  job.interior = k.dtype_bytes == 8 ? SMX_INTERIOR_F64 : smx_get_interior();
-  job.lead = k.channels;
-  job.n = total;
-  job.x_stride = k.cap;
+  StftJob job = stft_job(c, k.d_stream, k.dtype_bytes, k.channels, total, k.cap, 0, count, k.mode, k.power, k.d_out, stream);
   job.left = 0;                 // the stream is already padded
   job.pad = SMX_PAD_CONSTANT;
   job.pad_value = 0.0;
-  job.p0 = 0;
-  job.count = count;
-  job.mode = k.mode;
-  job.power = k.power;
-  job.out = k.d_out;
-  job.out_stride = count;
-  job.out_offset = 0;
-  job.stream = stream;
   launch_stft(job);
   // [channels; bins; count] (dense) -> caller's [channels; bins; capacity] window
   const size_t vs = (size_t)k.values() * es;
@@ -1451,14 +1385,10 @@ void mel_apply_host(const smx_mel_config &c, const void *s, int elem_bytes, int6
   check_mel_shape(c, lead, bins, frames);
   if (lead == 0 || frames == 0) return;
   if (!s || !out) throw Failure("apply: null pointer");
-  require_device();
-  const size_t in_bytes = (size_t)lead * (size_t)bins * (size_t)frames * (size_t)elem_bytes;
-  const size_t out_bytes = (size_t)lead * (size_t)c.n_mels * (size_t)frames * (size_t)elem_bytes;
-  DeviceScratch ds(in_bytes), dout(out_bytes);
-  copy_to_device(ds.ptr, s, in_bytes);
-  mel_apply_dev(c, ds.ptr, elem_bytes, lead, bins, frames, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, out_bytes);
+  host_call("mel_apply", {{s, (size_t)bins * (size_t)frames * (size_t)elem_bytes}}, out, (size_t)c.n_mels * (size_t)frames * (size_t)elem_bytes,
+            lead, false, nullptr, [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mel_apply_dev(c, d_in[0], elem_bytes, nc, bins, frames, d_out, stream);
+            });
 }
 
 void check_fft_sizes(const smx_stft_config &sc, const smx_mel_config &mc) {  // soundml.ml:12-20
@@ -1482,21 +1412,7 @@ void mel_spectrogram_dev(const smx_stft_config &sc, const smx_mel_config &mc, co
   if (lead == 0 || count == 0) return;
   if (!d_x || !d_out) throw Failure("mel_spectrogram: null device pointer");
   MelSpecJob job;
-  job.stft.cfg = &sc;
-  job.stft.x = d_x;
-  job.stft.in_bytes = in_bytes;
-  job.stft.interior = in_bytes == 8 ? SMX_INTERIOR_F64 : g_interior.load();
-  job.stft.lead = lead;
-  job.stft.n = n;
-  job.stft.x_stride = x_stride;
-  job.stft.left = sc.left_width();
-  job.stft.pad = sc.pad;
-  job.stft.pad_value = sc.pad_value;
-  job.stft.p0 = 0;
-  job.stft.count = count;
-  job.stft.mode = OUT_POWER;
-  job.stft.power = power;
-  job.stft.stream = stream;
+  job.stft = stft_job(sc, d_x, in_bytes, lead, n, x_stride, 0, count, OUT_POWER, power, nullptr, stream);
   job.mel = &mc;
   job.out = d_out;
   if (launch_mel_spectrogram_fused(job)) return;
@@ -1505,28 +1421,9 @@ void mel_spectrogram_dev(const smx_stft_config &sc, const smx_mel_config &mc, co
   const size_t bytes = (size_t)lead * (size_t)sc.bins() * (size_t)count * (size_t)in_bytes;
   SMX_HIP_CHECK(smx::pool_malloc_async(&scratch, bytes, stream));
   job.stft.out = scratch;
-  job.stft.out_stride = count;
-  job.stft.out_offset = 0;
   launch_stft(job.stft);
   mel_apply_dev(mc, scratch, in_bytes, lead, sc.bins(), count, d_out, stream);
   SMX_HIP_CHECK(hipFreeAsync(scratch, stream));
-}
-
-void mel_spectrogram_host_one(const smx_stft_config &sc, const smx_mel_config &mc, const void *x, int in_bytes,
-                              int64_t lead, int64_t n, double power, void *out) {
-  check_fft_sizes(sc, mc);
-  check_rank_extents("mel_spectrogram", lead, n);
-  const int64_t count = sc.frames(n);
-  if (lead == 0 || count == 0) return;
-  if (!x || !out) throw Failure("mel_spectrogram: null pointer");
-  require_device();
-  const size_t in_total = (size_t)lead * (size_t)n * (size_t)in_bytes;
-  const size_t out_total = (size_t)lead * (size_t)mc.n_mels * (size_t)count * (size_t)in_bytes;
-  DeviceScratch dx(in_total), dout(out_total);
-  copy_to_device(dx.ptr, x, in_total);
-  mel_spectrogram_dev(sc, mc, dx.ptr, in_bytes, lead, n, n, power, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, out_total);
 }
 
 // Soundml.mel_spectrogram from host memory: the current device, or the device list's clip ranges side by side (soundml.mli:85-101:
@@ -1538,12 +1435,10 @@ void mel_spectrogram_host(const smx_stft_config &sc, const smx_mel_config &mc, c
   const int64_t count = sc.frames(n);
   if (lead == 0 || count == 0) return;
   if (!x || !out) throw Failure("mel_spectrogram: null pointer");
-  require_device();
-  const size_t in_clip = (size_t)n * (size_t)in_bytes, out_clip = (size_t)mc.n_mels * (size_t)count * (size_t)in_bytes;
-  for_each_shard(lead, [&](int64_t clip0, int64_t nc) {
-    mel_spectrogram_host_one(sc, mc, reinterpret_cast<const unsigned char *>(x) + (size_t)clip0 * in_clip, in_bytes, nc, n, power,
-                             reinterpret_cast<unsigned char *>(out) + (size_t)clip0 * out_clip);
-  });
+  host_call("mel_spectrogram", {{x, (size_t)n * (size_t)in_bytes}}, out, (size_t)mc.n_mels * (size_t)count * (size_t)in_bytes, lead, true,
+            nullptr, [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mel_spectrogram_dev(sc, mc, d_in[0], in_bytes, nc, n, n, power, d_out, stream);
+            });
 }
 
 
@@ -1633,26 +1528,7 @@ void griffin_lim_dev(const smx_stft_config &c, const void *d_s, int elem_bytes, 
   bool frame_major = false;
   const int64_t fm_rows = (frames + 15) / 16 * 16, fm_pitch = 1032;   // (rows of 8256 bytes: whole 64-byte blocks)
   auto fm_analysis_job = [&](const void *x, void *out) {
-    StftJob job;
-    job.cfg = &c;
-    job.x = x;
-    job.in_bytes = 4;
-    job.interior = g_interior.load();
-    job.lead = lead;
-    job.n = natural;
-    job.x_stride = natural;
-    job.left = c.left_width();
-    job.pad = c.pad;
-    job.pad_value = c.pad_value;
-    job.p0 = 0;
-    job.count = frames;
-    job.mode = OUT_COMPLEX;
-    job.power = 0.0;
-    job.out = out;
-    job.out_stride = frames;
-    job.out_offset = 0;
-    job.stream = stream;
-    return job;
+    return stft_job(c, x, 4, lead, natural, natural, 0, frames, OUT_COMPLEX, 0.0, out, stream);
   };
   if (folded && elem_bytes == 4 && env_flag("SMX_GL_FRAME_MAJOR") != 0 && c.frames(natural) == frames && lead <= 65535) {   // (the transposition's grid: a clip per blockIdx.z)
     IstftJob probe = make_job(nullptr, 0, 0, nullptr, natural);
@@ -1755,16 +1631,11 @@ void griffin_lim_host(const smx_stft_config &c, const void *s, int elem_bytes, i
     return;
   }
   if (!out || (frames > 0 && !s)) throw Failure("griffin_lim: null pointer");
-  require_device();
-  const size_t sb = (size_t)lead * (size_t)bins * (size_t)frames * (size_t)elem_bytes;
-  const size_t ob = (size_t)lead * (size_t)out_len * (size_t)elem_bytes;
-  DeviceScratch ds(sb), dp(phase ? sb : 16), dout(ob);
-  if (sb) copy_to_device(ds.ptr, s, sb);
-  if (phase && sb) copy_to_device(dp.ptr, phase, sb);
-  griffin_lim_dev(c, ds.ptr, elem_bytes, lead, bins, frames, n_iter, momentum, phase ? dp.ptr : nullptr, has_length,
-                  length, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, ob);
+  const size_t s_clip = (size_t)bins * (size_t)frames * (size_t)elem_bytes;
+  host_call("griffin_lim", {{s, s_clip}, {phase, s_clip}}, out, (size_t)out_len * (size_t)elem_bytes, lead, false, nullptr,
+            [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              griffin_lim_dev(c, d_in[0], elem_bytes, nc, bins, frames, n_iter, momentum, d_in[1], has_length, length, d_out, stream);
+            });
 }
 
 // Soundml.mfcc (soundml.ml:50-95): checks in the reference's order and words, then mel_spectrogram + the tail
@@ -1815,14 +1686,10 @@ void mfcc_host(const smx_stft_config &sc, const smx_mel_config &mc, const void *
   const int64_t count = sc.frames(n);
   if (lead == 0 || count == 0) return;
   if (!x || !out) throw Failure("mfcc: null pointer");
-  require_device();
-  const size_t in_total = (size_t)lead * (size_t)n * (size_t)in_bytes;
-  const size_t out_total = (size_t)lead * (size_t)n_mfcc * (size_t)count * (size_t)in_bytes;
-  DeviceScratch dx(in_total), dout(out_total);
-  copy_to_device(dx.ptr, x, in_total);
-  mfcc_dev(sc, mc, dx.ptr, in_bytes, lead, n, n, n_mfcc, has_lifter, lifter, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, out_total);
+  host_call("mfcc", {{x, (size_t)n * (size_t)in_bytes}}, out, (size_t)n_mfcc * (size_t)count * (size_t)in_bytes, lead, false, nullptr,
+            [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mfcc_dev(sc, mc, d_in[0], in_bytes, nc, n, n, n_mfcc, has_lifter, lifter, d_out, stream);
+            });
 }
 
 // ---- Convert.power_to_db / amplitude_to_db (convert.ml:3-62) ------------------------------------------------
@@ -1965,15 +1832,11 @@ void spectral_host(const SpectralParams &q, const void *s, int elem_bytes, int64
   check_spectral(q, lead, bins, frames);
   if (lead == 0 || bins == 0 || frames == 0) return;
   if (!s || !out) throw Failure(format("%s: null pointer", spectral_op(q.feature)));
-  require_device();
-  const size_t in_total = (size_t)lead * (size_t)bins * (size_t)frames * (size_t)elem_bytes;
-  const size_t out_total = (size_t)lead * (size_t)frames * (size_t)elem_bytes;
-  DeviceScratch ds(in_total), dout(out_total), dc(q.has_centroid ? out_total : 0);
-  copy_to_device(ds.ptr, s, in_total);
-  if (q.has_centroid) copy_to_device(dc.ptr, centroid, out_total);
-  spectral_dev(q, ds.ptr, elem_bytes, lead, bins, frames, dc.ptr, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, out_total);
+  const size_t row = (size_t)frames * (size_t)elem_bytes;
+  host_call(spectral_op(q.feature), {{s, (size_t)bins * row}, {centroid, row}}, out, row, lead, false, nullptr,
+            [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              spectral_dev(q, d_in[0], elem_bytes, nc, bins, frames, d_in[1], d_out, stream);
+            });
 }
 
 // ---- Chroma.apply / Soundml.chroma_stft (chroma.ml:285-317, soundml.ml:97-107) ------------------------------
@@ -2018,14 +1881,11 @@ void chroma_apply_host(const smx_chroma_config &c, const void *s, int elem_bytes
     return;
   }
   if (!s || !out) throw Failure("apply: null pointer");
-  require_device();
-  const size_t in_total = (size_t)lead * (size_t)bins * (size_t)frames * (size_t)elem_bytes;
-  const size_t out_total = (size_t)lead * (size_t)c.n_chroma * (size_t)frames * (size_t)elem_bytes;
-  DeviceScratch ds(in_total), dout(out_total);
-  copy_to_device(ds.ptr, s, in_total);
-  chroma_apply_dev(c, ds.ptr, elem_bytes, lead, bins, frames, norm, norm_p, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, out_total);
+  host_call("chroma_apply", {{s, (size_t)bins * (size_t)frames * (size_t)elem_bytes}}, out,
+            (size_t)c.n_chroma * (size_t)frames * (size_t)elem_bytes, lead, false, nullptr,
+            [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              chroma_apply_dev(c, d_in[0], elem_bytes, nc, bins, frames, norm, norm_p, d_out, stream);
+            });
 }
 
 void check_chroma_stft(const smx_stft_config &sc, const smx_chroma_config &cc) {   // soundml.ml:98-106
@@ -2059,14 +1919,10 @@ void chroma_stft_host(const smx_stft_config &sc, const smx_chroma_config &cc, co
   const int64_t count = sc.frames(n);
   if (lead == 0 || count == 0) return;
   if (!x || !out) throw Failure("chroma_stft: null pointer");
-  require_device();
-  const size_t in_total = (size_t)lead * (size_t)n * (size_t)in_bytes;
-  const size_t out_total = (size_t)lead * (size_t)cc.n_chroma * (size_t)count * (size_t)in_bytes;
-  DeviceScratch dx(in_total), dout(out_total);
-  copy_to_device(dx.ptr, x, in_total);
-  chroma_stft_dev(sc, cc, dx.ptr, in_bytes, lead, n, n, power, norm, norm_p, dout.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, dout.ptr, out_total);
+  host_call("chroma_stft", {{x, (size_t)n * (size_t)in_bytes}}, out, (size_t)cc.n_chroma * (size_t)count * (size_t)in_bytes, lead, false,
+            nullptr, [&](auto d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              chroma_stft_dev(sc, cc, d_in[0], in_bytes, nc, n, n, power, norm, norm_p, d_out, stream);
+            });
 }
 
 }  // namespace

@@ -1072,23 +1072,6 @@ smx_fir_plan::~smx_fir_plan() {
 
 using namespace smx;
 
-namespace {
-template <typename F>
-int guarded_fir(F &&body) {
-  try {
-    body();
-    return SMX_OK;
-  } catch (const InvalidArgument &e) {
-    set_last_error(e.what());
-    return SMX_INVALID_ARGUMENT;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return SMX_FAILURE;
-  }
-}
-
-}  // namespace
-
 namespace smx {
 // y[c][i] = (h * x[c])[out_shift + i], i in [0, n_out): the convolution of n input samples (zeros outside), any window of it
 void fir_apply_window_dev(const smx_fir_plan &p, const float *d_x, int64_t channels, int64_t n, int64_t x_stride,
@@ -1241,18 +1224,18 @@ extern "C" int smx_debug_read_stamps_fir(unsigned long long *out, int count) {
 extern "C" {
 
 int smx_fir_kaiser_beta(double attenuation_db, double *out) {
-  return guarded_fir([&] { *out = kaiser_beta(attenuation_db); });
+  return guarded([&] { *out = kaiser_beta(attenuation_db); });
 }
 
 int smx_fir_design_lowpass(int64_t taps, double cutoff, double beta, double *h) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!h && taps > 0) throw Failure("design_lowpass: null output");
     design_lowpass(taps, cutoff, beta, h);
   });
 }
 
 int smx_fir_plan_create(const double *h, int64_t taps, smx_fir_plan **out) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!out) throw Failure("fir_plan_create: null output handle");
     if (taps < 1)
       throw InvalidArgument(format("fir_plan_create: cannot filter with %lld taps (taps must be at least 1)",
@@ -1284,40 +1267,27 @@ int64_t smx_fir_plan_block(const smx_fir_plan *p) { return p ? p->nfft : -1; }
 
 int smx_fir_apply_f32_dev(const smx_fir_plan *p, const float *d_x, int64_t channels, int64_t n,
                           int64_t x_stride, float *d_y, int64_t y_stride, void *stream) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!p) throw Failure("fir_apply: null plan");
     fir_apply_dev(*p, d_x, channels, n, x_stride, d_y, y_stride, (hipStream_t)stream);
   });
 }
 
 int smx_fir_apply_f32(const smx_fir_plan *p, const float *x, int64_t channels, int64_t n, float *y) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!p) throw Failure("fir_apply: null plan");
     if (channels < 0 || n < 0) throw Failure("fir_apply: negative extent");
     if (channels == 0 || n == 0) return;
     if (!x || !y) throw Failure("fir_apply: null pointer");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
-      throw Failure("soundml_amd: no HIP device is available (this library has no CPU fallback)");
+    require_device();
     const size_t bytes = (size_t)channels * (size_t)n * sizeof(float);
-    float *dx = nullptr, *dy = nullptr;
-    SMX_HIP_CHECK(hipMalloc((void **)&dx, bytes));
-    if (hipMalloc((void **)&dy, bytes) != hipSuccess) {
-      (void)hipFree(dx);
-      throw Failure("fir_apply: device allocation failed");
-    }
-    try {
-      SMX_HIP_CHECK(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
-      fir_apply_dev(*p, dx, channels, n, n, dy, n, nullptr);
-      SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-      SMX_HIP_CHECK(hipMemcpy(y, dy, bytes, hipMemcpyDeviceToHost));
-    } catch (...) {
-      (void)hipFree(dx);
-      (void)hipFree(dy);
-      throw;
-    }
-    (void)hipFree(dx);
-    (void)hipFree(dy);
+    DeviceScratch dx, dy;
+    dx.alloc(bytes);
+    dy.alloc(bytes);
+    SMX_HIP_CHECK(hipMemcpy(dx.ptr, x, bytes, hipMemcpyHostToDevice));
+    fir_apply_dev(*p, dx.as<float>(), channels, n, n, dy.as<float>(), n, nullptr);
+    SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
+    SMX_HIP_CHECK(hipMemcpy(y, dy.ptr, bytes, hipMemcpyDeviceToHost));
   });
 }
 
@@ -1458,29 +1428,6 @@ void shape_dev(const double *d_x, const double *d_h, double *d_y, int64_t lines,
   SMX_HIP_CHECK(hipGetLastError());
 }
 
-// Device scratch that is released on every way out of a function (a throwing launch or check included): stream-ordered
-// (the retained pool) when a stream is given, plain hipMalloc / hipFree otherwise.
-struct DeviceScratch {
-  void *p = nullptr;
-  hipStream_t stream = nullptr;
-  bool pooled = false;
-  DeviceScratch() = default;
-  DeviceScratch(const DeviceScratch &) = delete;
-  DeviceScratch &operator=(const DeviceScratch &) = delete;
-  void alloc_async(size_t bytes, hipStream_t st) {
-    stream = st;
-    pooled = true;
-    SMX_HIP_CHECK(smx::pool_malloc_async(&p, bytes, st));
-  }
-  void alloc(size_t bytes) { SMX_HIP_CHECK(hipMalloc(&p, bytes)); }
-  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-  ~DeviceScratch() {
-    if (!p) return;
-    if (pooled) (void)hipFreeAsync(p, stream);
-    else (void)hipFree(p);
-  }
-};
-
 int64_t stage_out_length(const smx_resample_stage &s, int64_t n) { return (n * s.l + s.m - 1) / s.m; }   // ceil(n L / M)
 
 // blocks of the polyphase form: pairs [pair0, pair0 + pairs) of every channel; x[s - x0] = sample s for x_lo <= s < x_hi
@@ -1576,7 +1523,7 @@ int64_t kernel_step_dev(smx_resample_kernel &k, const float *d_x, int64_t n, int
   }
   const int64_t a_stride = (alen + 1) & ~int64_t(1);
   DeviceScratch av;   // [carry ++ chunk], as ols_run assembles it (resample.ml:1487-1507)
-  av.alloc_async((size_t)k.channels * (size_t)a_stride * sizeof(float), stream);
+  av.pool((size_t)k.channels * (size_t)a_stride * sizeof(float), stream);
   copy_rows(av.as<float>(), a_stride, k.carry, k.carry_cap, pend, k.channels, stream);
   copy_rows(av.as<float>() + pend, a_stride, d_x, x_stride, n, k.channels, stream);
   k.fed += n;
@@ -1634,7 +1581,7 @@ void stage_apply_dev(const smx_resample_stage &s, const float *d_x, int64_t chan
   if (s.l > 1) {
     n_in = n * s.l;
     in_stride = (n_in + 1) & ~int64_t(1);
-    xu.alloc_async((size_t)channels * (size_t)in_stride * sizeof(float), stream);
+    xu.pool((size_t)channels * (size_t)in_stride * sizeof(float), stream);
     const int64_t gx = std::min<int64_t>((n_in + 255) / 256, 2048);
     SMX_LAUNCH(smx::zero_stuff_kernel, dim3((unsigned)gx, (unsigned)channels), dim3(256), 0, stream, d_x, n, x_stride, (int)s.l,
                xu.as<float>(), in_stride);
@@ -1646,7 +1593,7 @@ void stage_apply_dev(const smx_resample_stage &s, const float *d_x, int64_t chan
     smx::fir_apply_window_dev(*s.fir, xin, channels, n_in, in_stride, d_y, y_stride, n_out, shift, stream);
   } else {
     const int64_t nv = (n_out - 1) * s.m + 1, v_stride = (nv + 1) & ~int64_t(1);
-    v.alloc_async((size_t)channels * (size_t)v_stride * sizeof(float), stream);
+    v.pool((size_t)channels * (size_t)v_stride * sizeof(float), stream);
     smx::fir_apply_window_dev(*s.fir, xin, channels, n_in, in_stride, v.as<float>(), v_stride, nv, shift, stream);
     const int64_t gy = std::min<int64_t>((n_out + 255) / 256, 2048);
     SMX_LAUNCH(smx::decimate_kernel, dim3((unsigned)gy, (unsigned)channels), dim3(256), 0, stream, v.as<float>(), v_stride, (int)s.m, d_y,
@@ -1654,19 +1601,13 @@ void stage_apply_dev(const smx_resample_stage &s, const float *d_x, int64_t chan
   }
   SMX_HIP_CHECK(hipGetLastError());
 }
-
-void require_hip_device() {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
-    throw Failure("soundml_amd: no HIP device is available (this library has no CPU fallback)");
-}
 }  // namespace
 
 extern "C" {
 
 int smx_resample_ols_geom(int64_t rate, int64_t l, int64_t m, int64_t k, int64_t *n, int64_t *b, int64_t *delta,
                           int *eligible) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (rate < 1 || l < 1 || m < 1 || k < 0) throw Failure("ols_geom: invalid stage");
     int64_t nn = 0, bb = 0, dd = 0;
     const bool ok = ols_geom_host(rate, l, m, k, nn, bb, dd);
@@ -1678,7 +1619,7 @@ int smx_resample_ols_geom(int64_t rate, int64_t l, int64_t m, int64_t k, int64_t
 }
 
 int smx_resample_prototype(int64_t l, int64_t k, double fc, double beta, double *h) {
-  return guarded_fir([&] {   // resample.ml:145-163 `design_prototype`: right half evaluated, left half mirrored, sum = L
+  return guarded([&] {   // resample.ml:145-163 `design_prototype`: right half evaluated, left half mirrored, sum = L
     if (l < 1 || k < 0) throw Failure("design_prototype: invalid stage");
     if (!h) throw Failure("design_prototype: null output");
     const int64_t mid = k * l, n = 2 * mid + 1;
@@ -1700,32 +1641,32 @@ int smx_resample_prototype(int64_t l, int64_t k, double fc, double beta, double 
 
 int smx_resample_shape_c128_dev(const double *d_x, const double *d_h, double *d_y, int64_t lines, int64_t n, int64_t sl,
                                 int64_t sm, void *stream) {
-  return guarded_fir([&] { shape_dev(d_x, d_h, d_y, lines, n, sl, sm, (hipStream_t)stream); });
+  return guarded([&] { shape_dev(d_x, d_h, d_y, lines, n, sl, sm, (hipStream_t)stream); });
 }
 
 int smx_resample_shape_c128(const double *x, const double *h, double *y, int64_t lines, int64_t n, int64_t sl, int64_t sm) {
-  return guarded_fir([&] {
+  return guarded([&] {
     int64_t w = 0;
     shape_check(lines, n, sl, sm, w);
     if (lines == 0) return;
     if (!x || !h || !y) throw Failure("soundml_resample_shape: null pointer");
-    require_hip_device();
+    require_device();
     const size_t xb = (size_t)lines * (size_t)(n / 2 + 1) * 16, hb = (size_t)(sl > 1 ? w / 2 + 1 : n / 2 + 1) * 16,
                  yb = (size_t)lines * (size_t)(w / 2 + 1) * 16;
     DeviceScratch dx, dh, dy;   // a failed second or third allocation releases the earlier ones
     dx.alloc(xb);
     dh.alloc(hb);
     dy.alloc(yb);
-    SMX_HIP_CHECK(hipMemcpy(dx.p, x, xb, hipMemcpyHostToDevice));
-    SMX_HIP_CHECK(hipMemcpy(dh.p, h, hb, hipMemcpyHostToDevice));
+    SMX_HIP_CHECK(hipMemcpy(dx.ptr, x, xb, hipMemcpyHostToDevice));
+    SMX_HIP_CHECK(hipMemcpy(dh.ptr, h, hb, hipMemcpyHostToDevice));
     shape_dev(dx.as<double>(), dh.as<double>(), dy.as<double>(), lines, n, sl, sm, nullptr);
     SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    SMX_HIP_CHECK(hipMemcpy(y, dy.p, yb, hipMemcpyDeviceToHost));
+    SMX_HIP_CHECK(hipMemcpy(y, dy.ptr, yb, hipMemcpyDeviceToHost));
   });
 }
 
 int smx_resample_stage_create(const double *proto, int64_t l, int64_t m, int64_t k, smx_resample_stage **out) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!out) throw Failure("resample_stage_create: null output handle");
     if (l < 1 || m < 1 || k < 0)
       throw InvalidArgument(format("resample_stage_create: cannot build a x%lld / %lld stage of group delay %lld "
@@ -1765,42 +1706,33 @@ int64_t smx_resample_stage_out_length(const smx_resample_stage *s, int64_t n) { 
 
 int smx_resample_stage_apply_f32_dev(const smx_resample_stage *s, const float *d_x, int64_t channels, int64_t n,
                                      int64_t x_stride, float *d_y, int64_t y_stride, void *stream) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!s) throw Failure("resample_stage: null stage");
     stage_apply_dev(*s, d_x, channels, n, x_stride, d_y, y_stride, (hipStream_t)stream);
   });
 }
 
 int smx_resample_stage_apply_f32(const smx_resample_stage *s, const float *x, int64_t channels, int64_t n, float *y) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!s) throw Failure("resample_stage: null stage");
     if (channels < 0 || n < 0) throw Failure("resample_stage: negative extent");
     const int64_t n_out = stage_out_length(*s, n);
     if (channels == 0 || n_out == 0) return;
     if (!x || !y) throw Failure("resample_stage: null pointer");
-    require_hip_device();
-    float *dx = nullptr, *dy = nullptr;
-    SMX_HIP_CHECK(hipMalloc((void **)&dx, (size_t)channels * (size_t)n * sizeof(float)));
-    if (hipMalloc((void **)&dy, (size_t)channels * (size_t)n_out * sizeof(float)) != hipSuccess) {
-      (void)hipFree(dx);
-      throw Failure("resample_stage: device allocation failed");
-    }
-    try {
-      SMX_HIP_CHECK(hipMemcpy(dx, x, (size_t)channels * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-      stage_apply_dev(*s, dx, channels, n, n, dy, n_out, nullptr);
-      SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-      SMX_HIP_CHECK(hipMemcpy(y, dy, (size_t)channels * (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost));
-    } catch (...) {
-      (void)hipFree(dx); (void)hipFree(dy);
-      throw;
-    }
-    (void)hipFree(dx); (void)hipFree(dy);
+    require_device();
+    DeviceScratch dx, dy;
+    dx.alloc((size_t)channels * (size_t)n * sizeof(float));
+    dy.alloc((size_t)channels * (size_t)n_out * sizeof(float));
+    SMX_HIP_CHECK(hipMemcpy(dx.ptr, x, (size_t)channels * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    stage_apply_dev(*s, dx.as<float>(), channels, n, n, dy.as<float>(), n_out, nullptr);
+    SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
+    SMX_HIP_CHECK(hipMemcpy(y, dy.ptr, (size_t)channels * (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 
 /* ---- Resample.Kernel of one overlap-save stage (resample.mli:270-319) ---- */
 int smx_resample_kernel_prepare(const smx_resample_stage *s, int64_t channels, int64_t max_block, smx_resample_kernel **out) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!out) throw Failure("resample_kernel_prepare: null output handle");
     if (!s) throw Failure("resample_kernel_prepare: null stage");
     if (channels < 1 || max_block < 1)
@@ -1809,7 +1741,7 @@ int smx_resample_kernel_prepare(const smx_resample_stage *s, int64_t channels, i
     if (!s->poly)
       throw InvalidArgument(format("resample_kernel_prepare: cannot stream a x%lld / %lld stage block by block (only a pure xL or /M "
                                    "stage is overlap-save eligible)", (long long)s->l, (long long)s->m));
-    require_hip_device();
+    require_device();
     auto k = std::make_unique<smx_resample_kernel>();
     k->stage = s;
     k->channels = channels;
@@ -1824,7 +1756,7 @@ int smx_resample_kernel_prepare(const smx_resample_stage *s, int64_t channels, i
 }
 void smx_resample_kernel_destroy(smx_resample_kernel *k) { delete k; }
 int smx_resample_kernel_reset(smx_resample_kernel *k) {
-  return guarded_fir([&] {
+  return guarded([&] {
     if (!k) throw Failure("resample_kernel: null kernel");
     k->fed = k->emitted = k->pairs_done = k->carry_from = 0;
     k->drained = false;
@@ -1841,14 +1773,14 @@ int64_t smx_resample_kernel_pending(const smx_resample_kernel *k) { return k && 
 
 int smx_resample_kernel_step_f32_dev(smx_resample_kernel *k, const float *d_x, int64_t n, int64_t x_stride, float *d_y,
                                      int64_t y_stride, int64_t *n_out, void *stream) {
-  return guarded_fir([&] {
+  return guarded([&] {
     kernel_check(k);
     const int64_t got = kernel_step_dev(*k, d_x, n, x_stride, d_y, y_stride, (hipStream_t)stream);
     if (n_out) *n_out = got;
   });
 }
 int smx_resample_kernel_flush_f32_dev(smx_resample_kernel *k, float *d_y, int64_t y_stride, int64_t *n_out, void *stream) {
-  return guarded_fir([&] {
+  return guarded([&] {
     kernel_check(k);
     const int64_t got = kernel_flush_dev(*k, d_y, y_stride, (hipStream_t)stream);
     if (n_out) *n_out = got;
@@ -1857,7 +1789,7 @@ int smx_resample_kernel_flush_f32_dev(smx_resample_kernel *k, float *d_y, int64_
 /* host chunks [channels; n] (row stride x_stride) -> y [channels; *n_out] (row stride y_stride >= out_bound(n)) */
 int smx_resample_kernel_step_f32(smx_resample_kernel *k, const float *x, int64_t n, int64_t x_stride, float *y, int64_t y_stride,
                                  int64_t *n_out) {
-  return guarded_fir([&] {
+  return guarded([&] {
     kernel_check(k);
     if (n_out) *n_out = 0;
     if (n > 0 && (!x || x_stride < n)) throw Failure("resample_kernel_step: null chunk or stride smaller than the chunk");
@@ -1869,20 +1801,20 @@ int smx_resample_kernel_step_f32(smx_resample_kernel *k, const float *x, int64_t
     DeviceScratch dx, dy;
     dx.alloc((size_t)k->channels * (size_t)n * sizeof(float));
     dy.alloc((size_t)k->channels * (size_t)bound * sizeof(float));
-    SMX_HIP_CHECK(hipMemcpy2D(dx.p, (size_t)n * sizeof(float), x, (size_t)x_stride * sizeof(float), (size_t)n * sizeof(float),
+    SMX_HIP_CHECK(hipMemcpy2D(dx.ptr, (size_t)n * sizeof(float), x, (size_t)x_stride * sizeof(float), (size_t)n * sizeof(float),
                               (size_t)k->channels, hipMemcpyHostToDevice));
     const int64_t got = kernel_step_dev(*k, dx.as<float>(), n, n, dy.as<float>(), bound, nullptr);
     SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
     if (got > 0) {
       if (!y || y_stride < got) throw Failure("resample_kernel_step: null output or stride smaller than the emitted run");
-      SMX_HIP_CHECK(hipMemcpy2D(y, (size_t)y_stride * sizeof(float), dy.p, (size_t)bound * sizeof(float), (size_t)got * sizeof(float),
+      SMX_HIP_CHECK(hipMemcpy2D(y, (size_t)y_stride * sizeof(float), dy.ptr, (size_t)bound * sizeof(float), (size_t)got * sizeof(float),
                                 (size_t)k->channels, hipMemcpyDeviceToHost));
     }
     if (n_out) *n_out = got;
   });
 }
 int smx_resample_kernel_flush_f32(smx_resample_kernel *k, float *y, int64_t y_stride, int64_t *n_out) {
-  return guarded_fir([&] {
+  return guarded([&] {
     kernel_check(k);
     if (n_out) *n_out = 0;
     const int64_t pending = kernel_flush_pending(*k);
@@ -1895,7 +1827,7 @@ int smx_resample_kernel_flush_f32(smx_resample_kernel *k, float *y, int64_t y_st
     dy.alloc((size_t)k->channels * (size_t)pending * sizeof(float));
     const int64_t got = kernel_flush_dev(*k, dy.as<float>(), pending, nullptr);
     SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    SMX_HIP_CHECK(hipMemcpy2D(y, (size_t)y_stride * sizeof(float), dy.p, (size_t)pending * sizeof(float), (size_t)got * sizeof(float),
+    SMX_HIP_CHECK(hipMemcpy2D(y, (size_t)y_stride * sizeof(float), dy.ptr, (size_t)pending * sizeof(float), (size_t)got * sizeof(float),
                               (size_t)k->channels, hipMemcpyDeviceToHost));
     if (n_out) *n_out = got;
   });

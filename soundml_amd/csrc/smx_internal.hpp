@@ -424,4 +424,56 @@ struct MelSpecJob {
 bool launch_mel_spectrogram_fused(const MelSpecJob &job);   // stft_fast.hip; false = not eligible
 bool launch_mel_spectrogram_16(const MelSpecJob &job);      // stft_generic.hip: fft 512 / 1024
 
+// ---- the C ABI's entry points (capi.cpp, fir.hip) ----------------------------------------------------------------
+// body() as one entry point: InvalidArgument -> SMX_INVALID_ARGUMENT, any other exception -> SMX_FAILURE, its text in smx_last_error
+template <typename F>
+int guarded(F &&body) {
+  try {
+    body();
+    return SMX_OK;
+  } catch (const InvalidArgument &e) {
+    set_last_error(e.what());
+    return SMX_INVALID_ARGUMENT;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return SMX_FAILURE;
+  }
+}
+
+inline void require_device() {
+  int count = 0;
+  hipError_t err = hipGetDeviceCount(&count);
+  if (err != hipSuccess || count < 1)
+    throw Failure("soundml_amd: no HIP device is available (this library has no CPU fallback)");
+}
+
+// Device scratch released on every way out of a function (a throwing launch or check included).  DeviceScratch(bytes) is the
+// host-array entry points' form: stream-ordered on the null stream from the library's pool (hipFree of a GB-sized array costs more
+// than the kernels; the pool keeps it for the next call), 0 bytes taken as 16.  Otherwise pool(bytes, stream) on a stream, or
+// alloc(bytes): plain hipMalloc / hipFree.
+struct DeviceScratch {
+  void *ptr = nullptr;
+  hipStream_t stream = nullptr;
+  bool pooled = false;
+  DeviceScratch() = default;
+  explicit DeviceScratch(size_t bytes) {
+    init_device_pool();
+    pool(bytes ? bytes : 16, nullptr);
+  }
+  DeviceScratch(const DeviceScratch &) = delete;
+  DeviceScratch &operator=(const DeviceScratch &) = delete;
+  void pool(size_t bytes, hipStream_t st) {
+    stream = st;
+    pooled = true;
+    SMX_HIP_CHECK(pool_malloc_async(&ptr, bytes, st));
+  }
+  void alloc(size_t bytes) { SMX_HIP_CHECK(hipMalloc(&ptr, bytes)); }
+  template <class T> T *as() const { return reinterpret_cast<T *>(ptr); }
+  ~DeviceScratch() {
+    if (!ptr) return;
+    if (pooled) (void)hipFreeAsync(ptr, stream);
+    else (void)hipFree(ptr);
+  }
+};
+
 }  // namespace smx
