@@ -391,6 +391,62 @@ int smx_spectral_flatness_f64(const double *s, int64_t lead, int64_t bins, int64
 int smx_spectral_flatness_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, double amin,
                                   double power, float *d_out, void *stream);
 
+/* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
+ * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
+ * independent planes):
+ *   harm[b, t] = running median of kernel_h frames of row b, perc[b, t] = running median of kernel_p bins of
+ *   column t (hpss.ml:22-61); the window of index i is [i - k/2, i + k - 1 - k/2], the value rank k/2 of the
+ *   ascending window (the upper middle, never a mean), indices outside the axis reflected half-sample-
+ *   symmetrically with period 2 n for any overhang (hpss.ml:43-50, 69-75).  The medians SELECT: each is one of the
+ *   input values bit for bit, and both filters draw from the same values.
+ *   mask_h = f(harm, margin_h * perc), mask_p = f(perc, margin_p * harm), f(x, r) = x^p / (x^p + r^p) on the pair
+ *   rescaled by its pointwise maximum z (p = 1 the identity, p = 2 one multiply), 0.5 (unit margins) or 0 where z is
+ *   below the smallest positive normal; power = INFINITY: the strict comparison x > r as 0 / 1 (hpss.ml:309-347).
+ * kernel_h, kernel_p >= 1 (any size: one may be far larger than its axis), power > 0 or INFINITY, margins finite
+ * and >= 1: otherwise SMX_INVALID_ARGUMENT with the messages of hpss.ml:373-396, checked in that order before any
+ * device work.  Either result pointer may be NULL (that result is not computed); zero-size axes write nothing.
+ * NaN inputs give unspecified results, as in the reference; -0.0 orders below +0.0.
+ *
+ * smx_hpss_masks_*           hpss.ml:411-414  `hpss_masks`: -> mask_h, mask_p, shape and dtype of s
+ * smx_hpss_of_spectrogram_*  hpss.ml:416-420  `hpss_of_spectrogram`: -> s * mask_h, s * mask_p
+ * smx_hpss_of_stft_*         hpss.ml:436-459  `hpss_of_stft`: z interleaved complex [lead; bins; frames] in the layout
+ *                            smx_stft_transform writes; mag = |z| in the component width, the unit phase component by
+ *                            component (1 + 0i where mag = 0), -> (mag * mask) * phase_re + i (mag * mask) * phase_im
+ * smx_hpss_*                 hpss.ml:477-504  `hpss` / `harmonic` / `percussive`: audio x [lead; n] -> y_h, y_p [lead; n]:
+ *                            Stft.transform -> hpss_of_stft -> Stft.invert ~length:n per component, bit for bit those
+ *                            three calls; y_p = NULL is `harmonic`, y_h = NULL `percussive` (the other inversion is
+ *                            skipped).  The spectra stay on the device; the batch runs in clip chunks.  Also raises what
+ *                            Stft.invert raises (stft.ml:745-786).  float64 audio: the float64 interior, complex128.
+ * Host faces split `lead` over the device list (smx_set_devices) like every batch call.                         */
+int smx_hpss_masks_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h, int64_t kernel_p,
+                       double power, double margin_h, double margin_p, float *mask_h, float *mask_p);
+int smx_hpss_masks_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h, int64_t kernel_p,
+                       double power, double margin_h, double margin_p, double *mask_h, double *mask_p);
+int smx_hpss_masks_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                           int64_t kernel_p, double power, double margin_h, double margin_p, float *d_mask_h,
+                           float *d_mask_p, void *stream);
+int smx_hpss_of_spectrogram_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                                int64_t kernel_p, double power, double margin_h, double margin_p, float *h, float *p);
+int smx_hpss_of_spectrogram_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                                int64_t kernel_p, double power, double margin_h, double margin_p, double *h, double *p);
+int smx_hpss_of_spectrogram_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                                    int64_t kernel_p, double power, double margin_h, double margin_p, float *d_h,
+                                    float *d_p, void *stream);
+int smx_hpss_of_stft_c64(const float *z_c64, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                         int64_t kernel_p, double power, double margin_h, double margin_p, float *z_h, float *z_p);
+int smx_hpss_of_stft_c128(const double *z_c128, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                          int64_t kernel_p, double power, double margin_h, double margin_p, double *z_h, double *z_p);
+int smx_hpss_of_stft_c64_dev(const float *d_z_c64, int64_t lead, int64_t bins, int64_t frames, int64_t kernel_h,
+                             int64_t kernel_p, double power, double margin_h, double margin_p, float *d_z_h,
+                             float *d_z_p, void *stream);
+int smx_hpss_f32(const smx_stft_config *c, const float *x, int64_t lead, int64_t n, int64_t kernel_h, int64_t kernel_p,
+                 double power, double margin_h, double margin_p, float *y_h, float *y_p);
+int smx_hpss_f64(const smx_stft_config *c, const double *x, int64_t lead, int64_t n, int64_t kernel_h, int64_t kernel_p,
+                 double power, double margin_h, double margin_p, double *y_h, double *y_p);
+int smx_hpss_f32_dev(const smx_stft_config *c, const float *d_x, int64_t lead, int64_t n, int64_t kernel_h,
+                     int64_t kernel_p, double power, double margin_h, double margin_p, float *d_y_h, float *d_y_p,
+                     void *stream);
+
 /* ---- Chroma over a linear-frequency spectrum (chroma.ml:95-317; Soundml.chroma_stft, soundml.ml:97-107) --
  * Config: the float64 [n_chroma; bins] projection of chroma.ml:109-175 (Gaussian bumps in the wrapped
  * chroma distance, unit euclidean columns, optional octave envelope, rows rolled so row 0 is C).

@@ -2,7 +2,7 @@
 spectrogram, mel filterbank, FIR block convolution) behind the reference's own
 module names:
 
-    from soundml_amd import Stft, Mel, Chroma, Window, Fir, mel_spectrogram, mfcc, chroma_stft, spectral_centroid
+    from soundml_amd import Stft, Mel, Chroma, Hpss, Window, Fir, mel_spectrogram, mfcc, chroma_stft, spectral_centroid
 
 Everything computes in hand-written HIP kernels (gfx950) behind the C ABI of
 ``include/soundml_amd.h``; this package is the thin host mirror of
@@ -21,6 +21,8 @@ from . import convert as Convert
 from .features import mel_spectrogram, mfcc, chroma_stft, power_to_db, amplitude_to_db
 from .spectral import (spectral_centroid, spectral_bandwidth, spectral_rolloff, spectral_flatness,
                        spectral_centroid_stage, spectral_bandwidth_stage, spectral_rolloff_stage, spectral_flatness_stage)
+from . import hpss as Hpss
+from .hpss import hpss_masks, hpss_of_spectrogram, hpss_of_stft, hpss, harmonic, percussive
 from . import shard
 
 
@@ -64,5 +66,5 @@ def get_devices():
 
 
 __all__ = ["Stft", "Mel", "Chroma", "Convert", "Window", "Fir", "Resample", "mel_spectrogram", "mfcc", "chroma_stft", "power_to_db", "amplitude_to_db", "spectral_centroid",
-           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
+           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

@@ -119,6 +119,18 @@ SIGNATURES = {
     "smx_spectral_flatness_f32": (cint, [vp, i64, i64, i64, f64, f64, vp]),
     "smx_spectral_flatness_f64": (cint, [vp, i64, i64, i64, f64, f64, vp]),
     "smx_spectral_flatness_f32_dev": (cint, [vp, i64, i64, i64, f64, f64, vp, vp]),
+    "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
+    "smx_hpss_of_spectrogram_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_of_spectrogram_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_of_spectrogram_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
+    "smx_hpss_of_stft_c64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_of_stft_c128": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_of_stft_c64_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
+    "smx_hpss_f32": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_f64": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
+    "smx_hpss_f32_dev": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
     "smx_chroma_config_create": (cint, [i64, f64, f64, cint, f64, cint, i64, i64, C.POINTER(vp)]),
     "smx_chroma_config_destroy": (None, [vp]),
     "smx_chroma_config_n_chroma": (i64, [vp]),

@@ -146,40 +146,49 @@ struct HostIn {
   size_t clip_bytes;
 };
 
+// One result array of a host-pointer call: clip_bytes per clip.  A null host pointer is a result the caller does not want: no device
+// copy, no download, and the device function sees a null pointer.
+struct HostOut {
+  void *host;
+  size_t clip_bytes;
+};
+
 // The host-pointer form of a batch call of `lead` clips whose arguments the caller has checked: require_device, then per clip range
-// device copies of the inputs and of the result, upload, dev(d_in, d_out, nclips, stream), download.  dev enqueues the work of
-// nclips clips on `stream` with d_in[i] / d_out at their first clip.
+// device copies of the inputs and of the results, upload, dev(d_in, d_out, nclips, stream), download.  dev enqueues the work of
+// nclips clips on `stream` with d_in[i] / d_out[i] at their first clip.
 //   shard     the device list's clip ranges side by side (for_each_shard)
-//   pipeline  (one input) a large batch is cut into units of clips whose upload, kernels and download overlap (transfer.cpp; a
-//             unit's result is the slice of the whole call's bit for bit: the reference's per-slice law, stft_grid.ml:180-205),
-//             this configuration's tables built first.  SMX_HOST_PIPELINE=0: serially.
+//   pipeline  (one input, one result) a large batch is cut into units of clips whose upload, kernels and download overlap
+//             (transfer.cpp; a unit's result is the slice of the whole call's bit for bit: the reference's per-slice law,
+//             stft_grid.ml:180-205), this configuration's tables built first.  SMX_HOST_PIPELINE=0: serially.
 template <class Dev>
-void host_call(const char *name, std::initializer_list<HostIn> inputs, void *out, size_t out_clip, int64_t lead, bool shard,
+void host_call(const char *name, std::initializer_list<HostIn> inputs, std::initializer_list<HostOut> outputs, int64_t lead, bool shard,
                const smx_stft_config *pipeline, Dev &&dev) {
   require_device();
   const std::vector<HostIn> in(inputs);
+  const std::vector<HostOut> out(outputs);
   auto one = [&](int64_t clip0, int64_t nc) {
     static const bool trace = env_flag("SMX_HOST_TRACE") == 1;   // diagnostic: where a host call's time goes
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     std::deque<DeviceScratch> scratch;
-    std::vector<void *> d_in;
+    std::vector<void *> d_in, d_out;
     for (const HostIn &i : in) d_in.push_back(i.host ? scratch.emplace_back((size_t)nc * i.clip_bytes).ptr : nullptr);
-    DeviceScratch d_out((size_t)nc * out_clip);
+    for (const HostOut &o : out) d_out.push_back(o.host ? scratch.emplace_back((size_t)nc * o.clip_bytes).ptr : nullptr);
     const double t1 = now();
-    void *dst = reinterpret_cast<unsigned char *>(out) + (size_t)clip0 * out_clip;
-    const size_t in_clip = in[0].clip_bytes;
+    const size_t in_clip = in[0].clip_bytes, out_clip = out[0].clip_bytes;
     // (without page-locked staging memory the pipelined form cannot run: the serial path's plain hipMemcpy still completes the call)
-    if (pipeline && in.size() == 1 && nc >= 8 && (size_t)nc * (in_clip + out_clip) >= ((size_t)128 << 20) && in_clip > 0 &&
-        out_clip > 0 && env_flag("SMX_HOST_PIPELINE") != 0 && staging_available()) {
+    if (pipeline && in.size() == 1 && out.size() == 1 && nc >= 8 && (size_t)nc * (in_clip + out_clip) >= ((size_t)128 << 20) &&
+        in_clip > 0 && out_clip > 0 && env_flag("SMX_HOST_PIPELINE") != 0 && staging_available()) {
       int64_t unit = (int64_t)(((size_t)48 << 20) / std::max(in_clip, out_clip));   // ~48 MB of the larger side per unit
       unit = std::max<int64_t>(1, std::min<int64_t>(unit, (nc + 3) / 4));
       SMX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the scratch arrays come from the null stream's pool
       (void)pipeline->tables();                      // (lazy tables are built before the threads start)
-      pipelined_host_call(reinterpret_cast<const unsigned char *>(in[0].host) + (size_t)clip0 * in_clip, in_clip, dst, out_clip, nc, unit,
-                          d_in[0], d_out.ptr, [&](int64_t u0, int64_t un, hipStream_t stream) {
+      pipelined_host_call(reinterpret_cast<const unsigned char *>(in[0].host) + (size_t)clip0 * in_clip, in_clip,
+                          reinterpret_cast<unsigned char *>(out[0].host) + (size_t)clip0 * out_clip, out_clip, nc, unit, d_in[0], d_out[0],
+                          [&](int64_t u0, int64_t un, hipStream_t stream) {
                             const void *d_unit = reinterpret_cast<const unsigned char *>(d_in[0]) + (size_t)u0 * in_clip;
-                            dev(&d_unit, reinterpret_cast<unsigned char *>(d_out.ptr) + (size_t)u0 * out_clip, un, stream);
+                            void *d_result = reinterpret_cast<unsigned char *>(d_out[0]) + (size_t)u0 * out_clip;
+                            dev(&d_unit, &d_result, un, stream);
                           });
       if (trace) fprintf(stderr, "[smx] host %s: allocate %.2f ms, pipelined upload / kernels / download %.2f (units of %lld clips)\n", name, t1 - t0, now() - t1, (long long)unit);
       return;
@@ -188,16 +197,26 @@ void host_call(const char *name, std::initializer_list<HostIn> inputs, void *out
       if (in[i].host)
         copy_to_device(d_in[i], reinterpret_cast<const unsigned char *>(in[i].host) + (size_t)clip0 * in[i].clip_bytes, (size_t)nc * in[i].clip_bytes);
     const double t2 = now();
-    dev(d_in.data(), d_out.ptr, nc, nullptr);
+    dev(d_in.data(), d_out.data(), nc, nullptr);
     SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
     const double t3 = now();
-    copy_to_host(dst, d_out.ptr, (size_t)nc * out_clip);
+    for (size_t i = 0; i < out.size(); ++i)
+      if (out[i].host)
+        copy_to_host(reinterpret_cast<unsigned char *>(out[i].host) + (size_t)clip0 * out[i].clip_bytes, d_out[i], (size_t)nc * out[i].clip_bytes);
     if (trace)
       fprintf(stderr, "[smx] host %s: allocate %.2f ms, upload %.2f, kernels %.2f, download %.2f\n", name, t1 - t0, t2 - t1,
               t3 - t2, now() - t3);
   };
   if (shard) for_each_shard(lead, one);
   else one(0, lead);
+}
+
+// the common case: one result array
+template <class Dev>
+void host_call(const char *name, std::initializer_list<HostIn> inputs, void *out, size_t out_clip, int64_t lead, bool shard,
+               const smx_stft_config *pipeline, Dev &&dev) {
+  host_call(name, inputs, {HostOut{out, out_clip}}, lead, shard, pipeline,
+            [&](auto d_in, void *const *d_out, int64_t nc, hipStream_t stream) { dev(d_in, d_out[0], nc, stream); });
 }
 
 void check_config(const void *c, const char *fn) {
@@ -1839,6 +1858,129 @@ void spectral_host(const SpectralParams &q, const void *s, int elem_bytes, int64
             });
 }
 
+// ---- Hpss (hpss.ml:351-504): checks in the reference's order and words, then one launch ---------------------------------
+struct HpssParams {
+  const char *fn = "hpss";
+  int64_t kernel_h = 31, kernel_p = 31;
+  double power = 2.0, margin_h = 1.0, margin_p = 1.0;
+};
+
+// check_kernel, check_power, check_margin (hpss.ml:373-396); rank and dtype are what the entry point's signature states
+void check_hpss(const HpssParams &q) {
+  if (q.kernel_h < 1 || q.kernel_p < 1)
+    throw InvalidArgument(format("%s: cannot median-filter with a kernel of (%lld, %lld) (both kernel sizes must be at least 1)", q.fn,
+                                 (long long)q.kernel_h, (long long)q.kernel_p));
+  if (std::isnan(q.power) || q.power <= 0.0)
+    throw InvalidArgument(format("%s: cannot raise the mask to the power %g (power must be strictly positive, or infinite for a hard mask)",
+                                 q.fn, std::isnan(q.power) ? std::fabs(q.power) : q.power));
+  if (!(std::isfinite(q.margin_h) && std::isfinite(q.margin_p) && q.margin_h >= 1.0 && q.margin_p >= 1.0))
+    throw InvalidArgument(format("%s: cannot bias the decision by a margin of (%g, %g) (both margins must be finite and at least 1)", q.fn,
+                                 std::isnan(q.margin_h) ? std::fabs(q.margin_h) : q.margin_h,
+                                 std::isnan(q.margin_p) ? std::fabs(q.margin_p) : q.margin_p));
+}
+
+void check_hpss_plane(const HpssParams &q, int64_t lead, int64_t bins, int64_t frames) {
+  if (lead < 0 || bins < 0 || frames < 0)
+    throw Failure(format("%s: negative extent (lead %lld, bins %lld, frames %lld)", q.fn, (long long)lead, (long long)bins,
+                         (long long)frames));
+  check_hpss(q);
+}
+
+// hpss_masks / hpss_of_spectrogram / hpss_of_stft on device-resident planes; either result pointer may be null
+void hpss_dev(int mode, const HpssParams &q, const void *d_s, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, void *d_h,
+              void *d_p, hipStream_t stream) {
+  check_hpss_plane(q, lead, bins, frames);
+  if (lead == 0 || bins == 0 || frames == 0) return;   // nothing to separate
+  if (!d_s || (!d_h && !d_p)) throw Failure(format("%s: null device pointer", q.fn));
+  HpssJob job;
+  job.mode = mode;
+  job.s = d_s;
+  job.elem_bytes = elem_bytes;
+  job.lead = lead;
+  job.bins = bins;
+  job.frames = frames;
+  job.kernel_h = q.kernel_h;
+  job.kernel_p = q.kernel_p;
+  job.power = q.power;
+  job.margin_h = q.margin_h;
+  job.margin_p = q.margin_p;
+  job.out_h = d_h;
+  job.out_p = d_p;
+  job.stream = stream;
+  launch_hpss(job);
+}
+
+void hpss_host(int mode, const HpssParams &q, const void *s, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, void *h, void *p) {
+  check_hpss_plane(q, lead, bins, frames);
+  if (lead == 0 || bins == 0 || frames == 0) return;
+  if (!s || (!h && !p)) throw Failure(format("%s: null pointer", q.fn));
+  const size_t plane = (size_t)bins * (size_t)frames * (size_t)elem_bytes * (mode == HPSS_STFT ? 2 : 1);
+  host_call(q.fn, {{s, plane}}, {{h, plane}, {p, plane}}, lead, true, nullptr,
+            [&](auto d_in, void *const *d_out, int64_t nc, hipStream_t stream) {
+              hpss_dev(mode, q, d_in[0], elem_bytes, nc, bins, frames, d_out[0], d_out[1], stream);
+            });
+}
+
+// `separate` (hpss.ml:477-492): Stft.transform -> hpss_of_stft -> Stft.invert ~length:n of the components that are wanted.  The
+// checks of all three run before any device work
+void check_separate(const HpssParams &q, const smx_stft_config *c, int64_t lead, int64_t n) {
+  check_hpss(q);
+  check_config(c, q.fn);
+  check_rank_extents(q.fn, lead, n);
+  check_synthesis(*c, c->bins(), n, true);
+}
+
+// The three complex planes live in scratch and the batch goes through in clip chunks that keep them bounded: every clip is
+// analysed, separated and synthesised on its own (stft.mli:214-218), so a chunk's result is the slice of the whole batch's.
+void separate_dev(const HpssParams &q, const smx_stft_config &c, const void *d_x, int in_bytes, int64_t lead, int64_t n, void *d_h,
+                  void *d_p, hipStream_t stream) {
+  check_separate(q, &c, lead, n);
+  if (lead == 0 || n == 0) return;
+  if (!d_x || (!d_h && !d_p)) throw Failure(format("%s: null device pointer", q.fn));
+  const int64_t bins = c.bins(), frames = c.frames(n);
+  const size_t plane = (size_t)bins * (size_t)frames * 2 * (size_t)in_bytes;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(lead, (int64_t)(((size_t)256 << 20) / std::max<size_t>(plane, 1))));
+  init_device_pool();
+  DeviceScratch z, z_h, z_p;
+  z.pool(std::max<size_t>(16, (size_t)chunk * plane), stream);
+  if (d_h) z_h.pool(std::max<size_t>(16, (size_t)chunk * plane), stream);
+  if (d_p) z_p.pool(std::max<size_t>(16, (size_t)chunk * plane), stream);
+  const size_t row = (size_t)n * (size_t)in_bytes;
+  for (int64_t c0 = 0; c0 < lead; c0 += chunk) {
+    const int64_t nc = std::min(chunk, lead - c0);
+    stft_range_dev(c, reinterpret_cast<const unsigned char *>(d_x) + (size_t)c0 * row, in_bytes, nc, n, n, 0, frames, OUT_COMPLEX, 2.0,
+                   z.ptr, stream);
+    hpss_dev(HPSS_STFT, q, z.ptr, in_bytes, nc, bins, frames, z_h.ptr, z_p.ptr, stream);
+    if (d_h) invert_dev(c, z_h.ptr, 2 * in_bytes, nc, bins, frames, 1, n, reinterpret_cast<unsigned char *>(d_h) + (size_t)c0 * row, stream);
+    if (d_p) invert_dev(c, z_p.ptr, 2 * in_bytes, nc, bins, frames, 1, n, reinterpret_cast<unsigned char *>(d_p) + (size_t)c0 * row, stream);
+  }
+}
+
+void separate_host(const HpssParams &q, const smx_stft_config *c, const void *x, int in_bytes, int64_t lead, int64_t n, void *h, void *p) {
+  check_separate(q, c, lead, n);
+  if (lead == 0 || n == 0) return;
+  if (!x || (!h && !p)) throw Failure(format("%s: null pointer", q.fn));
+  const size_t row = (size_t)n * (size_t)in_bytes;
+  host_call(q.fn, {{x, row}}, {{h, row}, {p, row}}, lead, true, nullptr,
+            [&](auto d_in, void *const *d_out, int64_t nc, hipStream_t stream) {
+              separate_dev(q, *c, d_in[0], in_bytes, nc, n, d_out[0], d_out[1], stream);
+            });
+}
+
+HpssParams hpss_params(const char *fn, int64_t kernel_h, int64_t kernel_p, double power, double margin_h, double margin_p) {
+  HpssParams q;
+  q.fn = fn;
+  q.kernel_h = kernel_h;
+  q.kernel_p = kernel_p;
+  q.power = power;
+  q.margin_h = margin_h;
+  q.margin_p = margin_p;
+  return q;
+}
+
+// the signal face's name: `hpss` returns the pair, `harmonic` / `percussive` one of them (hpss.ml:494-504)
+const char *separate_name(const void *h, const void *p) { return h && p ? "hpss" : (h ? "harmonic" : (p ? "percussive" : "hpss")); }
+
 // ---- Chroma.apply / Soundml.chroma_stft (chroma.ml:285-317, soundml.ml:97-107) ------------------------------
 void check_chroma_norm(const char *op, int norm, double norm_p) {   // chroma.ml:30-40
   if (norm == SMX_CHROMA_NORM_NONE || norm == SMX_CHROMA_NORM_INF) return;
@@ -2176,6 +2318,61 @@ int smx_spectral_flatness_f32_dev(const float *d_s, int64_t lead, int64_t bins, 
     spectral_dev(q, d_s, 4, lead, bins, frames, nullptr, d_out, (hipStream_t)stream);
   });
 }
+
+// ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------
+#define SMX_HPSS_ARGS int64_t kernel_h, int64_t kernel_p, double power, double margin_h, double margin_p
+#define SMX_HPSS_Q(fn) hpss_params(fn, kernel_h, kernel_p, power, margin_h, margin_p)
+int smx_hpss_masks_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *mask_h, float *mask_p) {
+  return guarded([&] { hpss_host(HPSS_MASKS, SMX_HPSS_Q("hpss_masks"), s, 4, lead, bins, frames, mask_h, mask_p); });
+}
+int smx_hpss_masks_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, double *mask_h, double *mask_p) {
+  return guarded([&] { hpss_host(HPSS_MASKS, SMX_HPSS_Q("hpss_masks"), s, 8, lead, bins, frames, mask_h, mask_p); });
+}
+int smx_hpss_masks_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *d_mask_h, float *d_mask_p,
+                           void *stream) {
+  return guarded([&] {
+    hpss_dev(HPSS_MASKS, SMX_HPSS_Q("hpss_masks"), d_s, 4, lead, bins, frames, d_mask_h, d_mask_p, (hipStream_t)stream);
+  });
+}
+int smx_hpss_of_spectrogram_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *h, float *p) {
+  return guarded([&] { hpss_host(HPSS_SPECTROGRAM, SMX_HPSS_Q("hpss_of_spectrogram"), s, 4, lead, bins, frames, h, p); });
+}
+int smx_hpss_of_spectrogram_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, double *h, double *p) {
+  return guarded([&] { hpss_host(HPSS_SPECTROGRAM, SMX_HPSS_Q("hpss_of_spectrogram"), s, 8, lead, bins, frames, h, p); });
+}
+int smx_hpss_of_spectrogram_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *d_h, float *d_p,
+                                    void *stream) {
+  return guarded([&] {
+    hpss_dev(HPSS_SPECTROGRAM, SMX_HPSS_Q("hpss_of_spectrogram"), d_s, 4, lead, bins, frames, d_h, d_p, (hipStream_t)stream);
+  });
+}
+int smx_hpss_of_stft_c64(const float *z, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *z_h, float *z_p) {
+  return guarded([&] { hpss_host(HPSS_STFT, SMX_HPSS_Q("hpss_of_stft"), z, 4, lead, bins, frames, z_h, z_p); });
+}
+int smx_hpss_of_stft_c128(const double *z, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, double *z_h, double *z_p) {
+  return guarded([&] { hpss_host(HPSS_STFT, SMX_HPSS_Q("hpss_of_stft"), z, 8, lead, bins, frames, z_h, z_p); });
+}
+int smx_hpss_of_stft_c64_dev(const float *d_z, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *d_z_h, float *d_z_p,
+                             void *stream) {
+  return guarded([&] { hpss_dev(HPSS_STFT, SMX_HPSS_Q("hpss_of_stft"), d_z, 4, lead, bins, frames, d_z_h, d_z_p, (hipStream_t)stream); });
+}
+int smx_hpss_f32(const smx_stft_config *c, const float *x, int64_t lead, int64_t n, SMX_HPSS_ARGS, float *y_h, float *y_p) {
+  return guarded([&] { separate_host(SMX_HPSS_Q(separate_name(y_h, y_p)), c, x, 4, lead, n, y_h, y_p); });
+}
+int smx_hpss_f64(const smx_stft_config *c, const double *x, int64_t lead, int64_t n, SMX_HPSS_ARGS, double *y_h, double *y_p) {
+  return guarded([&] { separate_host(SMX_HPSS_Q(separate_name(y_h, y_p)), c, x, 8, lead, n, y_h, y_p); });
+}
+int smx_hpss_f32_dev(const smx_stft_config *c, const float *d_x, int64_t lead, int64_t n, SMX_HPSS_ARGS, float *d_y_h, float *d_y_p,
+                     void *stream) {
+  return guarded([&] {
+    const HpssParams q = SMX_HPSS_Q(separate_name(d_y_h, d_y_p));
+    check_hpss(q);
+    check_config(c, q.fn);
+    separate_dev(q, *c, d_x, 4, lead, n, d_y_h, d_y_p, (hipStream_t)stream);
+  });
+}
+#undef SMX_HPSS_ARGS
+#undef SMX_HPSS_Q
 
 // ---- Chroma (chroma.ml:95-317, soundml.ml:97-107) ---------------------------------------------------
 int smx_chroma_config_create(int64_t n_chroma, double tuning, double ctroct, int has_octwidth, double octwidth,

@@ -403,6 +403,23 @@ struct SpectralJob {
 // synchronises the stream to read that verdict
 bool launch_spectral(const SpectralJob &job);   // spectral.hip
 
+// Hpss (hpss.ml:342-347, 416-420, 436-459) over a device-resident plane stack [lead; bins; frames]: the two running medians, the
+// mask pair and what the face makes of it, in one kernel
+enum HpssMode { HPSS_MASKS = 0, HPSS_SPECTROGRAM = 1, HPSS_STFT = 2 };
+struct HpssJob {
+  int mode = HPSS_MASKS;
+  const void *s = nullptr;       // device [lead; bins; frames]; HPSS_STFT: interleaved complex
+  int elem_bytes = 4;            // component width: 4 = float32 / complex64, 8 = float64 / complex128
+  int64_t lead = 0, bins = 0, frames = 0;
+  int64_t kernel_h = 31, kernel_p = 31;
+  double power = 2.0;            // infinite: hard masks
+  double margin_h = 1.0, margin_p = 1.0;
+  void *out_h = nullptr, *out_p = nullptr;   // device, shape and element type of s; either may be null (not wanted)
+  hipStream_t stream = nullptr;
+};
+void launch_hpss(const HpssJob &job);             // hpss.hip
+bool hpss_takes_fast_path(const HpssJob &job);    // the 31 x 31 float32 tile kernel serves the job (else: the general one)
+
 // Chroma.apply (chroma.ml:285-317): float64 projection + per-frame normalisation, one rounding
 struct ChromaJob {
   const smx_chroma_config *config = nullptr;
