@@ -5,22 +5,20 @@
 //
 //   y[c][i] = sum_k h[k] x[c][i - k],  i in [0, n)
 //
-// Two consecutive real blocks of one channel are packed as ONE complex signal
-// z = a + i b: filtering with a real h commutes with the packing, so a single
-// complex FFT(N) -> pointwise multiply with H -> inverse FFT(N) yields both
-// blocks (real part / imaginary part) with no real-FFT post-pass.
-//
-// FFT: in-place Stockham (autosort) passes of radix 16 / 4 / 2 -- N = 16384 is
-// 16.16.16.4.  One workgroup of N/16 threads owns a block pair; every thread keeps 16
-// complex points in registers, so a pass is: read 16 (lane-contiguous, conflict free),
-// barrier, twiddle + register DFT, write 16 to the autosort positions, barrier.  LDS
-// addresses are XOR-swizzled (a ^ ((a >> 5) & 31)) which makes every pass's reads
-// conflict free and its writes at most 2-way (tools/sim_fir_fft.py).  The first
-// pass reads HBM straight into registers, the last inverse pass stores to HBM from
-// registers, the H multiply happens in registers between the two transforms and the
-// inverse is conj(FFT(conj(.))) with 1/N folded into H: 7 LDS round trips for
-// N = 16384.  Twiddles: one table read per pass and radix group, powers by binary
-// multiplication (depth <= 4).
+// One kernel per block length N (the plan picks N >= 4 taps where it can: 75 % of every block is kept):
+//   * taps <= 80: fir_direct_kernel, the sum itself from an LDS tile;
+//   * N = 1024 .. 16384: fir_ols_real_kernel.  A block of N real samples is ONE complex transform of M = N/2 points over its
+//     (even, odd) sample pairs, with the real-FFT post-pass, the product with H and the inverse's pre-pass as one pointwise stage
+//     over the bin pairs (k, M - k).  The transform is fft_device.hpp's in-place Stockham (autosort) passes of radix 16 / 4 / 2: a
+//     workgroup of M/16 threads owns a block, every thread keeps 16 complex points in registers, and a pass is: read 16
+//     (lane-contiguous, conflict free), barrier, twiddle + register DFT, write 16 to the autosort positions, barrier.  LDS addresses
+//     are XOR-swizzled (a ^ ((a >> 5) & 31)), which makes every pass's reads conflict free and its writes at most 2-way
+//     (tools/sim_fir_fft.py).  The first pass reads HBM straight into registers, the last inverse pass stores to HBM from registers;
+//     the inverse is conj(FFT(conj(.))) with its 1/M folded into H;
+//   * N = 32768: fir_ols_pk32_kernel, the same half-size transform M = 16384 = 16 x 1024 on the STFT pipeline's register form:
+//     packed-float32 radix-32 butterflies, a 1024-point sub-transform per half-wave, one LDS transposition per sub-transform.
+// The block grid advances by an even step, so every window starts on an even sample: 8-byte loads and stores.
+// How each kernel came to replace its predecessors, with the measurements: DESIGN.md 4.5.
 //
 // Algorithmic HBM bytes: 8 B per sample (4 in + 4 out) plus the (taps-1)/L halo.
 #include <cmath>
@@ -33,22 +31,19 @@
 struct smx_fir_plan {
   int64_t taps = 0;
   int64_t nfft = 0;      // N
-  int64_t valid = 0;     // L = N - taps + 1
   int log2n = 0;
   std::vector<double> h;
   struct Tables {
-    float2 *h_nat = nullptr;  // H[k] / N, natural order
     float2 *tw = nullptr;     // exp(-2 pi i j / N), j < N/2
-    // half-size real-transform kernel (M = N/2 complex points per block of N real samples)
+    // the half-size real transform (M = N/2 complex points per block of N real samples)
     float2 *h_half = nullptr; // H[k] / (4 M), k = 0 .. M  (the 1/2 of the real post-pass, the 1/2 of the inverse
                               // pre-pass and the inverse transform's 1/M folded in)
     float2 *tw_m = nullptr;   // exp(-2 pi i j / M), j < M/2
-    // wave-split kernel (N = 32768: sixteen 1024-point sub-transforms, one per wave): tables in the order its lanes read
-    float2 *h_split = nullptr;  // h_half[NS k' + r] at [1024 r + k'] (NS = M / 1024 sub-transforms: 16 or 8), h_half[M] at [M]
-    float2 *w_split = nullptr;  // exp(-2 pi i (NS k' + r) / N) at [1024 r + k']
-    float2 *tw_1k = nullptr;    // exp(-2 pi i j / 1024), j < 512
-    // register-pipeline kernel (fir_ols_pk32_kernel): W_1024^(l k1) in the order its lanes read it -- rows m < 15 hold the pair
-    // k1 = 2 m + 1, 2 m + 2 per lane l (a float4), then one row of k1 = 31 (as stft_fast_p32.hpp's twA4 / twA31)
+    // N = 32768 only (fir_ols_pk32_kernel: sixteen 1024-point sub-transforms), in the order its lanes read them
+    float2 *h_split = nullptr;  // h_half[16 k' + r] at [1024 r + k'], h_half[M] at [M]
+    float2 *w_split = nullptr;  // exp(-2 pi i (16 k' + r) / N) at [1024 r + k']
+    // W_1024^(l k1): rows m < 15 hold the pair k1 = 2 m + 1, 2 m + 2 per lane l (a float4), then one row of k1 = 31 (as
+    // stft_fast_p32.hpp's twA4 / twA31)
     float2 *tw_a32 = nullptr;
   };
   const Tables &tables() const;
@@ -68,85 +63,36 @@ unsigned brev_host(unsigned v, int bits) {
   return r;
 }
 
+// retired0 / retired1 are where the arguments of the retired kernels sat (taps .. h_nat, tw_1k); nothing reads them.  They keep
+// the layout the kernels below were measured with: the compiler groups the argument loads by it, and without them the register
+// allocation of fir_ols_real_kernel moves (42 -> 32 scalar registers, <12, false> 89 -> 74 vector registers).  Dropping them is
+// a change to time on the device, not a clean-up.
 struct FirArgs {
   const float *x;
   float *y;
   int64_t n, x_stride, y_stride;   // n: input samples per channel
   int64_t n_out, out_shift;         // convolution outputs [out_shift, out_shift + n_out) land at y[0 .. n_out)
-  int64_t taps, nfft, valid;
-  int log2n;
-  int64_t pairs_per_channel;
-  const float2 *h_nat;
+  int64_t retired0[6];
   const float2 *tw;     // exp(-2 pi i j / N), j < N/2
-  // half-size kernel
   const float2 *h_half; // H[k] / (4 M), k <= M
   const float2 *tw_m;   // exp(-2 pi i j / M), j < M/2
-  const float2 *h_split, *w_split, *tw_1k;   // wave-split kernel
-  const float2 *tw_a32;                      // register-pipeline kernel
+  const float2 *h_split, *w_split, *retired1, *tw_a32;   // fir_ols_pk32_kernel
   int64_t lead;         // samples of every circular result that are discarded (even, >= taps - 1)
   int64_t step;         // block advance = N - lead (even)
   int64_t blocks_per_channel;
-  int64_t channels;
+  int64_t channels;     // fir_ols_pk32_kernel (persistent: it walks channels x blocks_per_channel blocks)
 };
 
 using namespace fftdev;
-
-template <int LOG2N>
-__global__ void __launch_bounds__((1 << LOG2N) / 16) fir_ols_kernel(FirArgs a) {
-  constexpr int N = 1 << LOG2N, T = N / 16;
-  constexpr int RL = LastPass<LOG2N>::R, NSL = LastPass<LOG2N>::NS, GL = 16 / RL;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float2 *z = reinterpret_cast<float2 *>(smem);
-  const int tid = threadIdx.x;
-  const int64_t channel = blockIdx.x / a.pairs_per_channel;
-  const int64_t pair = blockIdx.x % a.pairs_per_channel;
-  const float *x = a.x + channel * a.x_stride;
-  float *y = a.y + channel * a.y_stride;
-  const int64_t base_a = (2 * pair) * a.valid - (a.taps - 1);      // first input of block a
-  const int64_t base_b = base_a + a.valid;
-  c32 r[16];
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {   // element tid + T*m: lane-contiguous HBM reads, zeros outside the stream
-    const int64_t sa = base_a + tid + T * m, sb = base_b + tid + T * m;
-    r[m].x = (sa >= 0 && sa < a.n) ? x[sa] : 0.0f;
-    r[m].y = (sb >= 0 && sb < a.n) ? x[sb] : 0.0f;
-  }
-  fft_passes<LOG2N, true>(r, z, tid, a.tw);
-  // Y = Z * H (1/N folded in); inverse = conj(FFT(conj(Y))): store conj(Y) for the second transform
-#pragma unroll
-  for (int i = 0; i < GL; ++i)
-#pragma unroll
-    for (int j = 0; j < RL; ++j) {
-      const int idx = out_index<RL, NSL, T>(tid, i, j);
-      const float2 hv = a.h_nat[idx];
-      const c32 yv = cmul(r[i * RL + j], c32{hv.x, hv.y});
-      z[swz(idx)] = make_float2(yv.x, -yv.y);
-    }
-  fft_passes<LOG2N, false>(r, z, tid, a.tw);
-  const int64_t out_a = (2 * pair) * a.valid, out_b = out_a + a.valid;
-  const int skip = (int)a.taps - 1;
-#pragma unroll
-  for (int i = 0; i < GL; ++i)
-#pragma unroll
-    for (int j = 0; j < RL; ++j) {
-      const int idx = out_index<RL, NSL, T>(tid, i, j) - skip;   // position inside the valid span
-      if (idx >= 0) {
-        const int64_t oa = out_a + idx - a.out_shift, ob = out_b + idx - a.out_shift;
-        if (oa >= 0 && oa < a.n_out) y[oa] = r[i * RL + j].x;      // Re(conj(.)) =  Re
-        if (ob >= 0 && ob < a.n_out) y[ob] = -r[i * RL + j].y;     // Im(conj(.)) = -Im
-      }
-    }
-}
 
 // ---- one real block per workgroup on the half-size transform --------------------------------------------------
 // A block of N real samples is ONE complex transform of M = N/2 points over its (even, odd) sample pairs:
 //   forward FFT_M  ->  real post-pass X[k] = (E - i w_k D) / 2  ->  Y = X H  ->  inverse pre-pass
 //   Z'[k] = ((Y[k] + conj Y[M-k]) + i conj(w_k) (Y[k] - conj Y[M-k])) / 2  ->  inverse FFT_M  ->  (y[2n], y[2n+1])
 // with E = Z[k] + conj Z[M-k], D = Z[k] - conj Z[M-k], w_k = exp(-2 pi i k / N).  Post-pass, product and pre-pass
-// are one pointwise stage over the pairs (k, M - k).  The workgroup has M/16 threads and M float2 of LDS: for the
-// 8192-tap plan 512 threads and 64 KB, so TWO workgroups share a CU and run out of phase -- one in its LDS
-// exchanges while the other is in its butterflies -- where the packed-pair kernel above (1024 threads, 128 KB: one
-// workgroup per CU, every wave in the same phase) pays VALU time plus LDS time.
+// are one pointwise stage over the pairs (k, M - k).  The workgroup has M/16 threads and M float2 of LDS: at
+// N = 16384 512 threads and 64 KB, so TWO workgroups share a CU and run out of phase -- one in its LDS
+// exchanges while the other is in its butterflies.
 // The block grid advances by an EVEN step (N - lead, lead = the even number >= taps - 1 of wrap-carrying samples
 // that are discarded), so every window starts on an even sample: 8-byte loads and stores.
 template <int LOG2M, bool ALIGNED>
@@ -239,170 +185,21 @@ __global__ void __launch_bounds__((1 << LOG2M) / 16, 4) fir_ols_real_kernel(FirA
     }
 }
 
-// ---- N = 32768: the half-size transform split over the workgroup's sixteen waves ---------------------------------
-// M = 16384 = 16 x 1024.  One radix-16 pass over the whole block (element n = n' + 1024 q: thread n' holds q = 0..15,
+// ---- N = 32768: the half-size transform on the frame pipeline's register form: fir_ols_pk32_kernel ---------------------------------
+// M = 16384 = 16 x 1024.  One radix-16 pass across the whole block (element n = n' + 1024 q: thread n' takes columns n' and n' + 512,
 // lane-contiguous 8-byte reads), then sixteen independent 1024-point transforms: bins k = 16 k' + r belong to sub-transform r,
 //   X[16 k' + r] = sum_n' w_1024^(n' k') [ w_M^(n' r) sum_q x[n' + 1024 q] w_16^(q r) ].
-// Sub-transform r is the work of WAVE r alone: its three passes exchange through the wave's own 8 KB of LDS with no workgroup
-// barrier (DS operations of a wave complete in order), so the sixteen waves drift out of phase and one wave's LDS round trips
-// overlap the others' butterflies.  The inverse mirrors it (decimation in time: the waves' sub-transforms first, then the
-// twiddles and ONE radix-16 pass across waves whose outputs are lane-contiguous sample pairs again).  Five workgroup barriers per
-// block where the pass-by-pass kernel has sixteen (it spends 42 % of its wave time waiting at them).  Measured on C4 (one box,
-// alternating processes): pass-by-pass 0.107 ms, wave-split 0.104, wave-split + persistent workgroups that request the next
-// block's samples before the last pass 0.098.  The pointwise stage
-// takes pairs (k, M - k) = (r, k') and (16 - r, 1023 - k') from two waves' regions; its tables are stored in that order.
-template <bool ALIGNED>
-__global__ void __launch_bounds__(1024, 4) fir_ols_split_kernel(FirArgs a) {
-  constexpr int M = 16384, T = 1024;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float2 *z = reinterpret_cast<float2 *>(smem);
-  const int tid = threadIdx.x;
-  // Persistent: one workgroup per CU (128 KB of LDS) walks blocks blockIdx.x, + gridDim.x, ...; the NEXT block's sixteen sample
-  // pairs are requested before the current block's last pass and stores, so a block no longer opens with an exposed trip to HBM.
-  auto load_block = [&](int64_t b, c32 (&v)[16]) {
-    const int64_t channel = b / a.blocks_per_channel, blk = b % a.blocks_per_channel;
-    const float *x = a.x + channel * a.x_stride;
-    const int64_t base = blk * a.step - a.lead;      // first sample of the window (even)
-    int tl = threadIdx.x;
-    asm volatile("" : "+v"(tl));
-    if (ALIGNED && base >= 0 && base + 2 * M <= a.n) {     // the whole window lies inside the stream (block-uniform)
-      const float2 *src = reinterpret_cast<const float2 *>(x + base) + tl;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float2 t = src[T * q];
-        v[q] = {t.x, t.y};
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int64_t g = base + 2 * (int64_t)(tl + T * q);
-        v[q].x = (g >= 0 && g < a.n) ? x[g] : 0.0f;
-        v[q].y = (g + 1 >= 0 && g + 1 < a.n) ? x[g + 1] : 0.0f;
-      }
-    }
-  };
-  const int64_t total = a.channels * a.blocks_per_channel;
-  c32 r[16], nxt[16];
-  load_block(blockIdx.x, nxt);
-  for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) r[q] = nxt[q];
-    {   // the radix-16 pass across the block, then w_M^(n' r)
-      const float2 w1 = a.tw_m[tid];
-      fft16(r);
-      c32 w[16];
-      twiddle_powers<16>(c32{w1.x, w1.y}, w);
-#pragma unroll
-      for (int j = 1; j < 16; ++j) r[j] = cmul(r[j], w[j]);
-      const int pos = swz(tid);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) z[1024 * j + pos] = make_float2(r[j].x, r[j].y);
-    }
-    __syncthreads();
-    int lane = tid & 63, wave = tid >> 6;
-    asm volatile("" : "+v"(lane));
-    float2 *zr = z + 1024 * wave;
-    fft_passes<10, false, true, float, true>(r, zr, lane, a.tw_1k);
-    // r[4 i + j] = bin k' = lane + 64 i + 256 j of this wave's sub-transform
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) zr[swz(lane + 64 * i + 256 * j)] = make_float2(r[4 * i + j].x, r[4 * i + j].y);
-    __syncthreads();
-    // pointwise stage (real post-pass, product with H, inverse pre-pass) over the pairs (k, M - k)
-    auto pair = [&](int rr, int kq, bool self) {
-      const int rp = (16 - rr) & 15, kp = rr ? 1023 - kq : ((1024 - kq) & 1023);
-      float2 *pa = z + 1024 * rr + swz(kq), *pb = z + 1024 * rp + swz(kp);
-      const float2 A = *pa, B = *pb;
-      const float2 w = a.w_split[1024 * rr + kq];
-      const float2 hk = a.h_split[1024 * rr + kq];
-      const float2 hp = (rr == 0 && kq == 0) ? a.h_split[M] : a.h_split[1024 * rp + kp];
-      const c32 E = {A.x + B.x, A.y - B.y}, D = {A.x - B.x, A.y + B.y};
-      const c32 t = cmul(D, c32{w.x, w.y});
-      const c32 Xk = {E.x + t.y, E.y - t.x};                  // E - i w D          (= 2 X[k])
-      const c32 Xp = {E.x - t.y, -(E.y + t.x)};               // conj(E + i w D)    (= 2 X[M-k])
-      const c32 Yk = cmul(Xk, c32{hk.x, hk.y}), Yp = cmul(Xp, c32{hp.x, hp.y});
-      const c32 P = {Yk.x + Yp.x, Yk.y - Yp.y}, Q = {Yk.x - Yp.x, Yk.y + Yp.y};
-      const c32 u = cmul(Q, c32{w.x, -w.y});                  // conj(w) Q
-      // the inverse runs as conj(FFT(conj .)): store the conjugates of Z'[k] = P + i conj(w) Q, Z'[M-k] = conj(P - i conj(w) Q)
-      *pa = make_float2(P.x - u.y, -(P.y + u.x));
-      if (!self) *pb = make_float2(P.x + u.y, P.y - u.x);
-    };
-    int tp = tid;
-    asm volatile("" : "+v"(tp));
-#pragma unroll
-    for (int m = 1; m < 8; ++m) {
-      pair(m, tp, false);
-      if (m == 4) __builtin_amdgcn_sched_barrier(0);
-    }
-    if (tp < 512) pair(8, tp, false);          // (8, k') with (8, 1023 - k')
-    else pair(0, tp - 512, tp == 512);         // (0, k') with (0, 1024 - k'), k' < 512; k' = 0 pairs with itself and carries bin M
-    if (tid == 0) pair(0, 512, true);          // k = M/2
-    __syncthreads();
-    int li = tid & 63;
-    asm volatile("" : "+v"(li));
-    float2 *zi = z + 1024 * (tid >> 6);
-    fft_passes<10, false, true, float, true>(r, zi, li, a.tw_1k);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) zi[swz(li + 64 * i + 256 * j)] = make_float2(r[4 * i + j].x, r[4 * i + j].y);
-    __syncthreads();
-    int to = tid;
-    asm volatile("" : "+v"(to));
-    {
-      const int pos = swz(to);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const float2 v = z[1024 * j + pos];
-        r[j] = {v.x, v.y};
-      }
-    }
-    __syncthreads();   // every wave holds its points: the next block's first pass may overwrite the buffer
-    if (b + gridDim.x < total) load_block(b + gridDim.x, nxt);   // in flight across the last pass and the stores (issuing it after the twiddles measured the same)
-    {
-      const float2 w1 = a.tw_m[to];
-      c32 w[16];
-      twiddle_powers<16>(c32{w1.x, w1.y}, w);
-#pragma unroll
-      for (int j = 1; j < 16; ++j) r[j] = cmul(r[j], w[j]);
-      fft16(r);
-    }
-    const int64_t channel = b / a.blocks_per_channel, blk = b % a.blocks_per_channel;
-    float *y = a.y + channel * a.y_stride;
-    const int64_t out0 = blk * a.step - a.out_shift;   // y index of the block's first kept sample
-    const bool whole = out0 >= 0 && out0 + a.step <= a.n_out;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int64_t s = 2 * (int64_t)(to + T * q) - a.lead;   // position inside the kept span (even)
-      if (s >= 0 && s < a.step) {
-        const int64_t o = out0 + s;
-        const float re = r[q].x, im = -r[q].y;   // conj(FFT(conj .))
-        if (ALIGNED && whole) {
-          *reinterpret_cast<float2 *>(y + o) = make_float2(re, im);
-        } else {
-          if (o >= 0 && o < a.n_out) y[o] = re;
-          if (o + 1 >= 0 && o + 1 < a.n_out) y[o + 1] = im;
-        }
-      }
-    }
-  }
-}
-
-// ---- N = 32768 on the frame pipeline's register form (round 6): fir_ols_pk32_kernel ---------------------------------------------
-// What bounded fir_ols_split_kernel (profiles/r06/fir_channels.log, profiles/r07 PMC): 22-27 us per block and CU whatever the channel
-// count -- ~3000 vector instructions per thread x 16 waves (a third of them address arithmetic of the XOR-swizzled Stockham passes)
-// and nine to ten trips of the 128 KB block through LDS, one after the other because five workgroup barriers keep all sixteen waves
-// in the same phase.  Here the same decomposition M = 16384 = 16 x 1024 runs on the STFT pipeline's register form (stft_fast_p32.hpp):
+// The inverse mirrors it (decimation in time: the sub-transforms first, then the twiddles and ONE radix-16 pass across the block,
+// whose outputs are lane-contiguous sample pairs again).  On the STFT pipeline's register form (stft_fast_p32.hpp):
 //   * a 1024-point sub-transform lives in a HALF-WAVE, 32 lanes x 32 points, 1024 = 32 x 32: radix-32 in registers, the twiddle
 //     W_1024^(l k1) from an LDS table, ONE 32 x 32 transposition through the sub-transform's own LDS region (pitch-33 cells, conflict
-//     free), radix-32 in registers -- one LDS exchange per sub-transform where the Stockham form has two, no swizzle arithmetic;
+//     free), radix-32 in registers -- one LDS exchange per sub-transform and no swizzle arithmetic;
 //   * every butterfly is packed float32 (the generated v_pk_* stages of stft_pk_fft.inc, one issue slot per complex add / half a
 //     complex product), the twiddle powers of the cross-block passes and the pointwise stage too (pk_powers16, pk_ols_pairs1);
-//   * 512 threads (8 waves, 32 points a thread, up to 256 registers) instead of 1024 x 16 points.
-// Per block: radix-16 across the block (thread n' takes columns n' and n' + 512) -> [barrier] -> sub-transforms -> [barrier] -> pointwise
-// pairs (k, M - k) -> [barrier] -> sub-transforms -> [barrier] -> radix-16 across the block, stores.  Same arithmetic as the split kernel up
-// to the order of roundings inside a complex product (p32_cmul's form); parity is the FIR contract's (1e-5 sum|h|, tests).
+//   * 512 threads (8 waves, 32 points a thread, up to 256 registers), 139 KB of LDS: one persistent workgroup per CU walks the blocks.
+// Per block: radix-16 across the block -> [barrier] -> per wave, with no workgroup barrier: forward sub-transforms, pointwise pairs
+// (k, M - k), inverse sub-transforms -> [barrier] -> columns back into registers -> [barrier] -> radix-16 across the block, stores.
+// A complex product rounds in p32_cmul's order, not cmul's; parity is the FIR contract's (1e-5 sum|h|, tests).
 using f2 = float __attribute__((ext_vector_type(2)));
 #include "stft_pk_fft.inc"
 __device__ __forceinline__ void pk_fft32_nat(f2 (&v)[32]) {   // 32-point forward DFT, natural order in and out (stft_fast_p32.hpp: pk_fft32)
@@ -462,39 +259,23 @@ __device__ __forceinline__ void pk_sub1024(f2 (&v)[32], f2 (&t)[32], float *cell
 // 1 .. 7; wave 0: sub-transforms 0 and 8, which pair inside themselves).  Bin k = 16 k' + r pairs with M - k = 16 (1023 - k') + (16 - r):
 // lane l, register q of one half against lane 31 - l, register 31 - q of the other -- so forward sub-transform, pointwise stage and
 // inverse sub-transform are ONE chain inside the wave, through the wave's own LDS cells and with no workgroup barrier: the eight
-// waves drift apart and one wave's LDS round trips run under the others' butterflies (fir_ols_split_kernel held all sixteen waves
-// in one phase with a barrier either side of the pointwise stage and sent the block through LDS twice more).
+// waves drift apart and one wave's LDS round trips run under the others' butterflies.
 // Every pair is formed ONCE, by the member with q < 16: exchange 1 hands it the partner's registers 16 .. 31, exchange 2 returns
 // the partner's results.  Sub-transform 0 pairs (0, k') with (0, 1024 - k'): lane (32 - l) mod 32, and lane 0 pairs inside itself one
 // register further (k' = 32 q with 32 (32 - q)); k' = 0 (whose partner in the product is bin M) and k' = 512 pair with themselves.
-// NS = 16: N = 32768 (M = 16 x 1024), 512 threads, 139 KB of LDS, one workgroup per CU.  NS = 8: N = 16384 (M = 8 x 1024: filters of
-// up to 4096 taps at 75 % kept, up to 8192 at 50 %), 256 threads with FOUR columns each, 73.5 KB of LDS: TWO workgroups per CU, whose
-// barrier-separated phases interleave -- what one block of 128 KB cannot have.
-template <int NS> struct PkRadix;
-template <> struct PkRadix<16> {
-  static __device__ __forceinline__ void dft(f2 (&v)[16]) { pk_fft16(v); }
-  static __device__ __forceinline__ void twiddle(f2 (&v)[16], f2 w1) {
-    f2 w[16];
-    w[1] = w1;
-    pk_powers16(w);
-    pk_twiddle8(v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8]);
-    pk_twiddle7(v[9], v[10], v[11], v[12], v[13], v[14], v[15], w[9], w[10], w[11], w[12], w[13], w[14], w[15]);
-  }
-};
-template <> struct PkRadix<8> {
-  static __device__ __forceinline__ void dft(f2 (&v)[8]) { pk_fft8(v); }
-  static __device__ __forceinline__ void twiddle(f2 (&v)[8], f2 w1) {
-    f2 w[16];
-    w[1] = w1;
-    pk_powers8(w);
-    pk_twiddle7(v[1], v[2], v[3], v[4], v[5], v[6], v[7], w[1], w[2], w[3], w[4], w[5], w[6], w[7]);
-  }
-};
-template <int NS> constexpr size_t pk_lds_bytes() { return (size_t)NS * 1024 * sizeof(float2) + kPkTwBytes; }
+// v *= W_M^(n' r), r = 1 .. 15, from w1 = W_M^(n'): the twiddles of the radix-16 passes across the block
+__device__ __forceinline__ void pk_twiddle16(f2 (&v)[16], f2 w1) {
+  f2 w[16];
+  w[1] = w1;
+  pk_powers16(w);
+  pk_twiddle8(v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8]);
+  pk_twiddle7(v[9], v[10], v[11], v[12], v[13], v[14], v[15], w[9], w[10], w[11], w[12], w[13], w[14], w[15]);
+}
+constexpr size_t kPkLdsBytes = (size_t)16 * 1024 * sizeof(float2) + kPkTwBytes;   // the block, then the W_1024 table
 
-template <bool ALIGNED, int NS>
-__global__ void __launch_bounds__(32 * NS) fir_ols_pk32_kernel(FirArgs a) {
-  constexpr int M = 1024 * NS, T = 32 * NS, CPT = 1024 / T;   // threads, columns per thread (2 / 4): CPT x NS = 32 points a thread
+template <bool ALIGNED>
+__global__ void __launch_bounds__(512) fir_ols_pk32_kernel(FirArgs a) {
+  constexpr int NS = 16, M = 1024 * NS, T = 32 * NS, CPT = 1024 / T;   // sub-transforms, points, threads, columns per thread (2): CPT x NS = 32 points a thread
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   f2 *z = reinterpret_cast<f2 *>(smem);   // [16][1024]: sub-transform r at z + 1024 r
   const float4 *twA4 = reinterpret_cast<const float4 *>(smem + (size_t)M * sizeof(float2));
@@ -545,13 +326,13 @@ __global__ void __launch_bounds__(32 * NS) fir_ols_pk32_kernel(FirArgs a) {
   load_block(blockIdx.x, na);
   __syncthreads();   // the twiddle table
   for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
-    {   // radix-NS across the block, then W_M^(n' r): u_r[n'] for sub-transform r
+    {   // radix-16 across the block, then W_M^(n' r): u_r[n'] for sub-transform r
       int tw_ = tid;
       asm volatile("" : "+v"(tw_));
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        PkRadix<NS>::dft(na[c]);
-        PkRadix<NS>::twiddle(na[c], w1[c]);
+        pk_fft16(na[c]);
+        pk_twiddle16(na[c], w1[c]);
 #pragma unroll
         for (int r = 0; r < NS; ++r) z[1024 * r + tw_ + T * c] = na[c][r];
       }
@@ -632,8 +413,8 @@ __global__ void __launch_bounds__(32 * NS) fir_ols_pk32_kernel(FirArgs a) {
       for (int q = 0; q < 32; ++q) zr[l + 32 * q] = v[q];
     }
     // the next block's samples are requested HERE, before the barrier: the sub-transforms' registers are free, and the requests have
-    // the barrier, the last pass's LDS reads, its barrier and its arithmetic to arrive under (behind the second barrier, as the split
-    // kernel has them, a block opened with ~1 us of exposed HBM latency: eight waves do not cover it)
+    // the barrier, the last pass's LDS reads, its barrier and its arithmetic to arrive under (requested behind the
+    // second barrier, a block opened with ~1 us of exposed HBM latency: eight waves do not cover it)
     if (b + gridDim.x < total) load_block(b + gridDim.x, na);
     SMX_STAMP(4);
     __syncthreads();
@@ -649,8 +430,8 @@ __global__ void __launch_bounds__(32 * NS) fir_ols_pk32_kernel(FirArgs a) {
     SMX_STAMP(6);
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      PkRadix<NS>::twiddle(va[c], w1[c]);
-      PkRadix<NS>::dft(va[c]);
+      pk_twiddle16(va[c], w1[c]);
+      pk_fft16(va[c]);
     }
     SMX_STAMP(7);
     const int64_t channel = b / a.blocks_per_channel, blk = b % a.blocks_per_channel;
@@ -753,6 +534,7 @@ __global__ void __launch_bounds__(256) fir_direct_kernel(FirDirectArgs a) {
   }
 }
 
+
 // ---- resample stages ("Resample OLS stages -- true rate conversion on the FIR kernel") ----------
 // xu[c][q L] = x[c][q], zeros between: the interpolated-rate input of a xL stage
 __global__ void __launch_bounds__(256) zero_stuff_kernel(const float *x, int64_t n, int64_t x_stride, int l, float *xu,
@@ -777,8 +559,9 @@ __global__ void __launch_bounds__(256) decimate_kernel(const float *v, int64_t v
 // same arithmetic as the reference's spectral shortcut (one spectrum replicated L times against the prototype's on the fine
 // grid / folded M times, resample_stubs.c:329-372) regrouped so that every transform is a power of two at the LOW rate --
 // 1/L (1/M) of the flops of filtering the zero-stuffed signal, and no interpolated-rate scratch.
-// Overlap-save blocks of N points at the low rate, two real blocks per complex transform (the packed pair of
-// fir_ols_kernel): block pair P owns low-rate outputs [2 P V, 2 P V + 2 V), V = N - taps + 1, on a grid fixed to the stream's
+// Overlap-save blocks of N points at the low rate, two real blocks a, b per complex transform z = a + i b (filtering with a
+// real h commutes with the packing: the inverse's real part is block a's result, its imaginary part block b's, with no
+// real-FFT post-pass): block pair P owns low-rate outputs [2 P V, 2 P V + 2 V), V = N - taps + 1, on a grid fixed to the stream's
 // first sample -- so a streaming caller that runs pair P whenever its inputs are in computes the very values the offline
 // call does (the partition law of Resample.Kernel, resample.mli:296-317).
 struct PolyArgs {
@@ -972,7 +755,7 @@ const smx_fir_plan::Tables &smx_fir_plan::tables() const {
   std::lock_guard<std::mutex> lock(mutex_);
   auto it = tables_.find(device);
   if (it != tables_.end()) return it->second;
-  // H = DFT_N(h) in float64: iterative DIF (bit-reversed out), then unscrambled to natural order
+  // H = DFT_N(h) in float64: iterative DIF, position brev(k) of its output holds H[k]
   const int64_t N = nfft;
   std::vector<double> re((size_t)N, 0.0), im((size_t)N, 0.0);
   for (int64_t i = 0; i < taps; ++i) re[(size_t)i] = h[(size_t)i];
@@ -990,11 +773,7 @@ const smx_fir_plan::Tables &smx_fir_plan::tables() const {
       im[(size_t)i1] = dr * wi + di * wr;
     }
   }
-  std::vector<float2> hb((size_t)N), tw((size_t)(N / 2 > 0 ? N / 2 : 1));
-  for (int64_t i = 0; i < N; ++i) {
-    const unsigned k = smx::brev_host((unsigned)i, log2n);   // position i holds H[brev(i)]
-    hb[k] = make_float2((float)(re[(size_t)i] / (double)N), (float)(im[(size_t)i] / (double)N));
-  }
+  std::vector<float2> tw((size_t)(N / 2 > 0 ? N / 2 : 1));
   for (int64_t j = 0; j < N / 2; ++j) {
     const double ang = -2.0 * M_PI * (double)j / (double)N;
     tw[(size_t)j] = make_float2((float)std::cos(ang), (float)std::sin(ang));
@@ -1015,26 +794,19 @@ const smx_fir_plan::Tables &smx_fir_plan::tables() const {
     SMX_HIP_CHECK(hipMemcpy(t.h_half, hh.data(), hh.size() * sizeof(float2), hipMemcpyHostToDevice));
     SMX_HIP_CHECK(hipMalloc((void **)&t.tw_m, twm.size() * sizeof(float2)));
     SMX_HIP_CHECK(hipMemcpy(t.tw_m, twm.data(), twm.size() * sizeof(float2), hipMemcpyHostToDevice));
-    if (log2n == 15 || log2n == 14) {   // the split kernels' tables (M = NS x 1024 points, NS = 16 / 8 sub-transforms), in the order their lanes read them
-      const int64_t ns = M / 1024;
-      std::vector<float2> hs((size_t)M + 1), ws((size_t)M), t1k(512);
+    if (log2n == 15) {   // fir_ols_pk32_kernel's tables (M = 16 x 1024 points), in the order its lanes read them
+      std::vector<float2> hs((size_t)M + 1), ws((size_t)M);
       for (int64_t k = 0; k < M; ++k) {
-        const size_t at = (size_t)((k % ns) * 1024 + k / ns);
+        const size_t at = (size_t)((k % 16) * 1024 + k / 16);
         hs[at] = hh[(size_t)k];
         const double ang = -2.0 * M_PI * (double)k / (double)N;
         ws[at] = make_float2((float)std::cos(ang), (float)std::sin(ang));
       }
       hs[(size_t)M] = hh[(size_t)M];
-      for (int j = 0; j < 512; ++j) {
-        const double ang = -2.0 * M_PI * (double)j / 1024.0;
-        t1k[(size_t)j] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-      }
       SMX_HIP_CHECK(hipMalloc((void **)&t.h_split, hs.size() * sizeof(float2)));
       SMX_HIP_CHECK(hipMemcpy(t.h_split, hs.data(), hs.size() * sizeof(float2), hipMemcpyHostToDevice));
       SMX_HIP_CHECK(hipMalloc((void **)&t.w_split, ws.size() * sizeof(float2)));
       SMX_HIP_CHECK(hipMemcpy(t.w_split, ws.data(), ws.size() * sizeof(float2), hipMemcpyHostToDevice));
-      SMX_HIP_CHECK(hipMalloc((void **)&t.tw_1k, t1k.size() * sizeof(float2)));
-      SMX_HIP_CHECK(hipMemcpy(t.tw_1k, t1k.data(), t1k.size() * sizeof(float2), hipMemcpyHostToDevice));
       std::vector<float2> ta(31 * 32);
       auto w1k = [](int e) {
         const double ang = -2.0 * M_PI * (double)(e % 1024) / 1024.0;
@@ -1050,8 +822,6 @@ const smx_fir_plan::Tables &smx_fir_plan::tables() const {
       SMX_HIP_CHECK(hipMemcpy(t.tw_a32, ta.data(), ta.size() * sizeof(float2), hipMemcpyHostToDevice));
     }
   }
-  SMX_HIP_CHECK(hipMalloc((void **)&t.h_nat, hb.size() * sizeof(float2)));
-  SMX_HIP_CHECK(hipMemcpy(t.h_nat, hb.data(), hb.size() * sizeof(float2), hipMemcpyHostToDevice));
   SMX_HIP_CHECK(hipMalloc((void **)&t.tw, tw.size() * sizeof(float2)));
   SMX_HIP_CHECK(hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
   return tables_.emplace(device, t).first->second;
@@ -1059,13 +829,11 @@ const smx_fir_plan::Tables &smx_fir_plan::tables() const {
 
 smx_fir_plan::~smx_fir_plan() {
   for (auto &kv : tables_) {
-    (void)hipFree(kv.second.h_nat);
     (void)hipFree(kv.second.tw);
     (void)hipFree(kv.second.h_half);
     (void)hipFree(kv.second.tw_m);
     (void)hipFree(kv.second.h_split);
     (void)hipFree(kv.second.w_split);
-    (void)hipFree(kv.second.tw_1k);
     (void)hipFree(kv.second.tw_a32);
   }
 }
@@ -1089,17 +857,11 @@ void fir_apply_window_dev(const smx_fir_plan &p, const float *d_x, int64_t chann
   a.out_shift = out_shift;
   a.x_stride = x_stride;
   a.y_stride = y_stride;
-  a.taps = p.taps;
-  a.nfft = p.nfft;
-  a.valid = p.valid;
-  a.log2n = p.log2n;
-  a.h_nat = t.h_nat;
   a.tw = t.tw;
   a.h_half = t.h_half;
   a.tw_m = t.tw_m;
   a.h_split = t.h_split;
   a.w_split = t.w_split;
-  a.tw_1k = t.tw_1k;
   a.tw_a32 = t.tw_a32;
   static const bool direct_off = diag_flag("SMX_FIR_DIRECT") == 0;   // A/B timing: FFT blocks for short filters too
   static const int64_t direct_max = (int64_t)diag_int("SMX_FIR_DIRECT_MAX", 80);
@@ -1120,85 +882,33 @@ void fir_apply_window_dev(const smx_fir_plan &p, const float *d_x, int64_t chann
     SMX_HIP_CHECK(hipGetLastError());
     return;
   }
-  static const bool packed_env = diag_flag("SMX_FIR_PACKED") == 1;
-  const bool packed = packed_env && p.log2n <= 14;
-  if (!packed) {   // one real block per workgroup, half-size transform
-    a.lead = (p.taps - 1 + 1) & ~int64_t(1);                 // even, >= taps - 1
-    a.step = p.nfft - a.lead;
-    a.blocks_per_channel = (out_shift + n_out + a.step - 1) / a.step;
-    const int64_t grid = channels * a.blocks_per_channel;
-    if (grid > 0x7fffffff) throw Failure("fir_apply: too many blocks for one launch");
-    const size_t lds = (size_t)(p.nfft / 2) * sizeof(float2);
-    const bool aligned = x_stride % 2 == 0 && y_stride % 2 == 0 && out_shift % 2 == 0 &&
-                         reinterpret_cast<uintptr_t>(d_x) % 8 == 0 && reinterpret_cast<uintptr_t>(d_y) % 8 == 0;
-    auto launch = [&](auto kernel, int threads) {
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      SMX_LAUNCH(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
-    };
-    switch (p.log2n) {
-      case 10: aligned ? launch(fir_ols_real_kernel<9, true>, 32) : launch(fir_ols_real_kernel<9, false>, 32); break;
-      case 11: aligned ? launch(fir_ols_real_kernel<10, true>, 64) : launch(fir_ols_real_kernel<10, false>, 64); break;
-      case 12: aligned ? launch(fir_ols_real_kernel<11, true>, 128) : launch(fir_ols_real_kernel<11, false>, 128); break;
-      case 13: aligned ? launch(fir_ols_real_kernel<12, true>, 256) : launch(fir_ols_real_kernel<12, false>, 256); break;
-      case 14: {
-        // N = 16384 stays on the Stockham kernel: the register pipeline with eight sub-transforms and TWO workgroups per CU (73.5 KB of LDS
-        // each) measured 4 % behind it (8192 taps 0.1316 against 0.1286 ms, 4096 taps 0.1008 / 0.0969, 3000 taps 0.0922 / 0.0882:
-        // profiles/r08/fir_time_n16384.log) -- two independent workgroups did not cover what bounds a wave there, its own chain of LDS round
-        // trips at two waves per SIMD.  SMX_FIR_PK=1 in diagnostic builds selects it (same results to rounding; A/B timing).
-        const bool stockham = diag_flag("SMX_FIR_PK") != 1;
-        if (stockham) aligned ? launch(fir_ols_real_kernel<13, true>, 512) : launch(fir_ols_real_kernel<13, false>, 512);
-        else {   // persistent, two workgroups per CU
-          a.channels = channels;
-          const int64_t slots = 2 * (int64_t)device_cu_count();
-          const unsigned g = (unsigned)(grid < slots ? grid : slots);
-          auto launch_p = [&](auto kernel) {
-            SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds_bytes<8>()));
-            SMX_LAUNCH(kernel, dim3(g), dim3(256), pk_lds_bytes<8>(), stream, a);
-          };
-          aligned ? launch_p(fir_ols_pk32_kernel<true, 8>) : launch_p(fir_ols_pk32_kernel<false, 8>);
-        }
-        break;
-      }
-      case 15: {
-        static const bool pass_by_pass = diag_flag("SMX_FIR_SPLIT") == 0;   // A/B timing
-        const bool split16 = diag_flag("SMX_FIR_PK") == 0;                 // A/B timing (read per launch): round 2-5's wave-split kernel
-        if (pass_by_pass) aligned ? launch(fir_ols_real_kernel<14, true>, 1024) : launch(fir_ols_real_kernel<14, false>, 1024);
-        else {
-          a.channels = channels;
-          const int64_t cus = device_cu_count();
-          const unsigned g = (unsigned)(grid < cus ? grid : cus);   // persistent: one workgroup per CU walks the blocks
-          auto launch_p = [&](auto kernel, int threads, size_t bytes) {
-            SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-            SMX_LAUNCH(kernel, dim3(g), dim3(threads), bytes, stream, a);
-          };
-          if (split16) aligned ? launch_p(fir_ols_split_kernel<true>, 1024, lds) : launch_p(fir_ols_split_kernel<false>, 1024, lds);
-          else aligned ? launch_p(fir_ols_pk32_kernel<true, 16>, 512, pk_lds_bytes<16>()) : launch_p(fir_ols_pk32_kernel<false, 16>, 512, pk_lds_bytes<16>());   // the register pipeline (round 6)
-        }
-        break;
-      }
-      default: throw Failure("fir_apply: unsupported block size");
-    }
-    SMX_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const int64_t blocks = (out_shift + n_out + p.valid - 1) / p.valid;
-  a.pairs_per_channel = (blocks + 1) / 2;
-  const int64_t grid = channels * a.pairs_per_channel;
+  // overlap-save: one real block per workgroup on the half-size transform
+  a.lead = (p.taps - 1 + 1) & ~int64_t(1);                 // even, >= taps - 1
+  a.step = p.nfft - a.lead;
+  a.blocks_per_channel = (out_shift + n_out + a.step - 1) / a.step;
+  a.channels = channels;
+  const int64_t grid = channels * a.blocks_per_channel;
   if (grid > 0x7fffffff) throw Failure("fir_apply: too many blocks for one launch");
-  const size_t lds = (size_t)p.nfft * sizeof(float2);
-  auto launch = [&](auto kernel, int threads) {
+  const bool aligned = x_stride % 2 == 0 && y_stride % 2 == 0 && out_shift % 2 == 0 &&
+                       reinterpret_cast<uintptr_t>(d_x) % 8 == 0 && reinterpret_cast<uintptr_t>(d_y) % 8 == 0;
+  auto launch = [&](auto kernel, int64_t workgroups, int threads, size_t lds) {
     SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SMX_LAUNCH(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
+    SMX_LAUNCH(kernel, dim3((unsigned)workgroups), dim3(threads), lds, stream, a);
   };
+  const int threads = (int)(p.nfft / 32);                        // M / 16
+  const size_t lds = (size_t)(p.nfft / 2) * sizeof(float2);      // M points
   switch (p.log2n) {
-    case 10: launch(fir_ols_kernel<10>, 64); break;
-    case 11: launch(fir_ols_kernel<11>, 128); break;
-    case 12: launch(fir_ols_kernel<12>, 256); break;
-    case 13: launch(fir_ols_kernel<13>, 512); break;
-    case 14: launch(fir_ols_kernel<14>, 1024); break;
+    case 10: aligned ? launch(fir_ols_real_kernel<9, true>, grid, threads, lds) : launch(fir_ols_real_kernel<9, false>, grid, threads, lds); break;
+    case 11: aligned ? launch(fir_ols_real_kernel<10, true>, grid, threads, lds) : launch(fir_ols_real_kernel<10, false>, grid, threads, lds); break;
+    case 12: aligned ? launch(fir_ols_real_kernel<11, true>, grid, threads, lds) : launch(fir_ols_real_kernel<11, false>, grid, threads, lds); break;
+    case 13: aligned ? launch(fir_ols_real_kernel<12, true>, grid, threads, lds) : launch(fir_ols_real_kernel<12, false>, grid, threads, lds); break;
+    case 14: aligned ? launch(fir_ols_real_kernel<13, true>, grid, threads, lds) : launch(fir_ols_real_kernel<13, false>, grid, threads, lds); break;
+    case 15: {   // persistent: one workgroup per CU walks the blocks
+      const int64_t g = std::min<int64_t>(grid, device_cu_count());
+      aligned ? launch(fir_ols_pk32_kernel<true>, g, 512, kPkLdsBytes) : launch(fir_ols_pk32_kernel<false>, g, 512, kPkLdsBytes);
+      break;
+    }
     default: throw Failure("fir_apply: unsupported block size");
   }
   SMX_HIP_CHECK(hipGetLastError());
@@ -1254,7 +964,6 @@ int smx_fir_plan_create(const double *h, int64_t taps, smx_fir_plan **out) {
     while (n < 4 * taps && n < (big ? 32768 : 16384)) n *= 2;
     while (n < 2 * taps) n *= 2;
     p->nfft = n;
-    p->valid = n - taps + 1;
     p->log2n = 0;
     while ((int64_t(1) << p->log2n) < n) ++p->log2n;
     p->h.assign(h, h + taps);
@@ -1290,7 +999,6 @@ int smx_fir_apply_f32(const smx_fir_plan *p, const float *x, int64_t channels, i
     SMX_HIP_CHECK(hipMemcpy(y, dy.ptr, bytes, hipMemcpyDeviceToHost));
   });
 }
-
 
 /* ---- Resample stages ------------------------------------------------------------------------------------------- */
 }  // extern "C"

@@ -1,5 +1,4 @@
 """C4 FIR timing (8192 taps, 8 x 2 880 000 samples, device resident; FIR_CH / FIR_NS: other batches) plus a parity check on one channel against the oracle.
-A/B of the two N = 32768 kernels: run once plain and once with SMX_FIR_SPLIT=0 (the switch is read once per process).
     python tools/fir_time.py [taps ...]
 """
 import ctypes
@@ -36,6 +35,6 @@ for taps in ([int(a) for a in sys.argv[1:]] or [8192]):
     ts.sort()
     want = O.fir_filter(h, x[3].cpu().numpy().astype(np.float64))
     err = float(np.max(np.abs(y[3].cpu().numpy() - want)))
-    print("taps %6d  N %6d  SMX_FIR_SPLIT=%s  min %.4f  median %.4f ms  (%.1f Gsamples/s, %.3f of 8 TB/s)  max abs err %.3g (bound %.3g)" % (
-        taps, plan.block, os.environ.get("SMX_FIR_SPLIT", "-"), ts[0], ts[len(ts) // 2], ch * ns / ts[len(ts) // 2] / 1e6,
+    print("taps %6d  N %6d  min %.4f  median %.4f ms  (%.1f Gsamples/s, %.3f of 8 TB/s)  max abs err %.3g (bound %.3g)" % (
+        taps, plan.block, ts[0], ts[len(ts) // 2], ch * ns / ts[len(ts) // 2] / 1e6,
         ch * ns * 8 / ts[len(ts) // 2] / 1e6 / 8000, err, 1e-5 * float(np.sum(np.abs(h)))))

@@ -380,7 +380,7 @@ def gen_ols_pairs(n):
        E = A + conj B, D = A - conj B, t = w D, X_k = E - i t, X_(M-k) = conj(E + i t), Y = X H,
        P = Y_k + conj Y_(M-k), Q = Y_k - conj Y_(M-k), u = conj(w) Q,
        A' = conj(P + i u) = (P.x - u.y, -(P.y + u.x)),  B' = P - i u = (P.x + u.y, P.y - u.x)
-    (the inverse transform runs as conj(FFT(conj .)), so the conjugates of Z'[k] are stored: fir_ols_split_kernel's `pair`)."""
+    (the inverse transform runs as conj(FFT(conj .)), so the conjugates of Z'[k] are stored)."""
     b = Block("pk_ols_pairs")
     A = {i: b.slot("io", "a%d" % i) for i in range(n)}
     B = {i: b.slot("io", "b%d" % i) for i in range(n)}
