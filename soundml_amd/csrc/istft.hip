@@ -384,76 +384,46 @@ __global__ void __launch_bounds__(FT * ((1 << LOG2N) / 32)) istft_stockham_frame
     }
 }
 
-template <int LOG2N, int FT, typename Tz>
-void launch_stockham_frames_wide(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
-  constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);
-  static_assert(THREADS <= 512, "16 complex doubles per thread need the 256-register budget");
-  const size_t planes = 2 * (size_t)(M + 1) * (FT + 1) * sizeof(double), work = (size_t)FT * M * sizeof(double2);
-  const size_t lds = (planes > work ? planes : work) + 16;
-  const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("invert: too many frame tiles for one launch");
-  auto kernel = istft_stockham_frames_wide_kernel<LOG2N, FT, Tz>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, stream, a, (const double2 *)t.fast_w_m_f64, (const double2 *)t.twiddle_f64,
-                     (const double2 *)t.fast_synth_window_f64);
-  SMX_HIP_CHECK(hipGetLastError());
+// the Stockham frames kernels' LDS: the two staging planes or the FT work buffers, whichever is larger
+template <typename S>
+constexpr size_t stockham_frames_lds(int M, int FT) {
+  const size_t planes = 2 * (size_t)(M + 1) * (FT + 1) * sizeof(S), work = (size_t)FT * M * 2 * sizeof(S);
+  return (planes > work ? planes : work) + 16;
 }
 
-template <typename Tz>
-bool launch_stockham_frames_wide_any(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
-  const bool fast_off = fast_path_disabled();
-  if (fast_off || diag_flag("SMX_ISTFT_RADIX2") == 1 || !t.fast_w_m_f64 || !t.twiddle_f64 || !t.fast_synth_window_f64) return false;
-  switch (a.fft) {
-    case 512: launch_stockham_frames_wide<9, 16, Tz>(a, t, stream); return true;
-    case 1024: launch_stockham_frames_wide<10, 8, Tz>(a, t, stream); return true;
-    case 2048: launch_stockham_frames_wide<11, 8, Tz>(a, t, stream); return true;
-    case 4096: launch_stockham_frames_wide<12, 2, Tz>(a, t, stream); return true;   // two float64 planes of 4 frames exceed the LDS
-    default: return false;
-  }
-}
-
-template <int LOG2N, int FT>
+// frames only (any hop), fft 512 .. 4096: Tz = float with S = float (complex64 spectra, float32 interior), Tz = float or double with
+// S = double (the float64 interior; two float64 planes of 4 frames exceed the LDS at fft 4096)
+template <int LOG2N, int FT, typename Tz, typename S>
 void launch_stockham_frames(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
   constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);
-  const size_t planes = 2 * (size_t)(M + 1) * (FT + 1) * sizeof(float), work = (size_t)FT * M * sizeof(float2);
-  const size_t lds = (planes > work ? planes : work) + 16;
   const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("invert: too many frame tiles for one launch");
-  auto kernel = istft_stockham_frames_kernel<LOG2N, FT, 0>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, stream, a, (const float2 *)t.fast_w_m, (const float2 *)t.fast_w_n,
-                     (const float2 *)t.fast_synth_window, FusedOla{});
-  SMX_HIP_CHECK(hipGetLastError());
-}
-
-// hop = N / 4 or N / 2: frames and overlap-add in one launch (fft 512 / 1024 / 2048)
-template <int LOG2N, int RATIO>
-bool launch_stockham_fused(const IstftArgs &a, const StftTables &t, const FusedOla &o, hipStream_t stream) {
-  constexpr int M = (1 << LOG2N) / 2, THREADS = 16 * (M / 16);
-  const size_t planes = 2 * (size_t)(M + 1) * 17 * sizeof(float), work = (size_t)16 * M * sizeof(float2);
-  const size_t lds = (planes > work ? planes : work) + 16;
-  const int64_t blocks = a.lead * (int64_t)o.tiles_per_clip;
-  if (blocks > 2147483647LL) return false;
-  auto kernel = istft_stockham_frames_kernel<LOG2N, 16, RATIO>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, stream, a, (const float2 *)t.fast_w_m, (const float2 *)t.fast_w_n,
-                     (const float2 *)t.fast_synth_window, o);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
-}
-
-// float32 spectra, float32 interior, fft 512 .. 4096: true when the Stockham frames kernel took the launch
-bool launch_stockham_frames_any(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
-  if (!t.fast_w_m || !t.fast_w_n || !t.fast_synth_window) return false;
-  const bool fast_off = fast_path_disabled();
-  if (fast_off) return false;
-  switch (a.fft) {
-    case 512: launch_stockham_frames<9, 16>(a, t, stream); return true;
-    case 1024: launch_stockham_frames<10, 16>(a, t, stream); return true;
-    case 2048: launch_stockham_frames<11, 16>(a, t, stream); return true;
-    case 4096: launch_stockham_frames<12, 8>(a, t, stream); return true;
-    default: return false;
+  if constexpr (sizeof(S) == 8) {
+    static_assert(THREADS <= 512, "16 complex doubles per thread need the 256-register budget");
+    launch_tiles("invert", istft_stockham_frames_wide_kernel<LOG2N, FT, Tz>, blocks, THREADS, stockham_frames_lds<double>(M, FT), stream, a,
+                 (const double2 *)t.fast_w_m_f64, (const double2 *)t.twiddle_f64, (const double2 *)t.fast_synth_window_f64);
+  } else {
+    launch_tiles("invert", istft_stockham_frames_kernel<LOG2N, FT, 0>, blocks, THREADS, stockham_frames_lds<float>(M, FT), stream, a,
+                 (const float2 *)t.fast_w_m, (const float2 *)t.fast_w_n, (const float2 *)t.fast_synth_window, FusedOla{});
   }
+}
+
+template <typename Tz, typename S>
+void launch_stockham_frames_any(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
+  constexpr int W = sizeof(S) == 8 ? 2 : 1;
+  switch (a.fft) {
+    case 512: return launch_stockham_frames<9, 16, Tz, S>(a, t, stream);
+    case 1024: return launch_stockham_frames<10, 16 / W, Tz, S>(a, t, stream);
+    case 2048: return launch_stockham_frames<11, 16 / W, Tz, S>(a, t, stream);
+    default: return launch_stockham_frames<12, W == 2 ? 2 : 8, Tz, S>(a, t, stream);
+  }
+}
+
+// hop = N / 4 or N / 2: frames and overlap-add in one launch (fft 512 / 1024 / 2048), a.lead * o.tiles_per_clip workgroups
+template <int LOG2N, int RATIO>
+void launch_stockham_fused(const IstftArgs &a, const StftTables &t, const FusedOla &o, hipStream_t stream) {
+  constexpr int M = (1 << LOG2N) / 2;
+  launch_tiles("invert", istft_stockham_frames_kernel<LOG2N, 16, RATIO>, a.lead * (int64_t)o.tiles_per_clip, 16 * (M / 16), stockham_frames_lds<float>(M, 16),
+               stream, a, (const float2 *)t.fast_w_m, (const float2 *)t.fast_w_n, (const float2 *)t.fast_synth_window, o);
 }
 
 struct OlaArgs {
@@ -786,31 +756,22 @@ __global__ void __launch_bounds__(64 * FT) istft_mixed_frames_kernel(IstftArgs a
 
 template <int LOG2LP, int FT, typename Tz, typename S, bool FULL = false>
 void launch_mixed_frames(const IstftArgs &a, const MixedInv<S> &pl, hipStream_t stream) {
-  const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("invert: too many frame tiles for one launch");
   const size_t lds = (size_t)(FT + 1) * 2 * (size_t(1) << LOG2LP) * sizeof(typename fftdev::vec2_of<S>::type);   // frames + the two twiddle tables
-  auto kernel = istft_mixed_frames_kernel<LOG2LP, FT, Tz, S, FULL>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(64 * FT), lds, stream, a, pl);
-  SMX_HIP_CHECK(hipGetLastError());
+  launch_tiles("invert", istft_mixed_frames_kernel<LOG2LP, FT, Tz, S, FULL>, a.lead * ((a.count + FT - 1) / FT), 64 * FT, lds, stream, a, pl);
 }
 
-// no Griffin-Lim factors: true when the mixed-radix frames kernel took the launch.  <float, float>: complex64 spectra, float32
-// interior; <float, double>: complex64 under the float64 interior; <double, double>: complex128.
+// a size with a mixed-radix plan (N / 2, or N for an odd size, = 2^a 3^b 5^c 7^d <= 1024; the powers of two 4 .. 256 among them), no
+// Griffin-Lim factors.  <float, float>: complex64 spectra, float32 interior; <float, double>: complex64 under the float64 interior;
+// <double, double>: complex128.
 template <typename Tz, typename S>
-bool launch_mixed_frames_any(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
-  if (t.mixed_npass <= 0 || a.mag || a.unit || (a.fft % 2 != 0) != (t.mixed_full != 0)) return false;
-  static const bool off = env_flag("SMX_MIXED_OFF") == 1;
-  if (off) return false;
+void launch_mixed_frames_any(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
   MixedInv<S> pl{};
   pl.npass = t.mixed_npass;
   for (int i = 0; i < t.mixed_npass; ++i) pl.radices |= (unsigned long long)t.mixed_radix[i] << (4 * i);
   if constexpr (sizeof(S) == 4) {
-    if (!t.mixed_tw || !t.twiddle_f32) return false;
     pl.tw_l = t.mixed_tw;
     pl.tw_n = (const float2 *)t.twiddle_f32;
   } else {
-    if (!t.mixed_tw_f64 || !t.twiddle_f64) return false;
     pl.tw_l = t.mixed_tw_f64;
     pl.tw_n = (const double2 *)t.twiddle_f64;
   }
@@ -820,23 +781,20 @@ bool launch_mixed_frames_any(const IstftArgs &a, const StftTables &t, hipStream_
     if (n <= 128) launch_mixed_frames<7, 16, Tz, S, true>(a, pl, stream);
     else if (n <= 256) launch_mixed_frames<8, 16 / W, Tz, S, true>(a, pl, stream);
     else if (n <= 512) launch_mixed_frames<9, 16 / W, Tz, S, true>(a, pl, stream);
-    else if (n <= 1024) launch_mixed_frames<10, 8 / W, Tz, S, true>(a, pl, stream);
-    else return false;
-    return true;
+    else launch_mixed_frames<10, 8 / W, Tz, S, true>(a, pl, stream);
+    return;
   }
   const int64_t l = a.fft / 2;
   if (l < 128) launch_mixed_frames<7, 16, Tz, S>(a, pl, stream);
   else if (l < 256) launch_mixed_frames<8, 16 / W, Tz, S>(a, pl, stream);
   else if (l < 512) launch_mixed_frames<9, 16 / W, Tz, S>(a, pl, stream);
-  else if (l < 1024) launch_mixed_frames<10, 8 / W, Tz, S>(a, pl, stream);
-  else return false;
-  return true;
+  else launch_mixed_frames<10, 8 / W, Tz, S>(a, pl, stream);
 }
 
 constexpr size_t kLdsLimit = 160 * 1024;
 
 template <typename Tz, typename Tacc>
-void launch_frames(const IstftJob &job, IstftArgs a, hipStream_t stream) {
+void launch_frames(IstftArgs a, hipStream_t stream) {
   const int64_t N = a.fft;
   const bool pow2 = (N & (N - 1)) == 0;
   auto lds_bytes = [&](int ft, bool p2) {
@@ -851,14 +809,20 @@ void launch_frames(const IstftJob &job, IstftArgs a, hipStream_t stream) {
   a.ft = ft;
   a.log2n = 0;
   while ((int64_t(1) << a.log2n) < N) ++a.log2n;
-  const int64_t blocks = a.lead * ((a.count + ft - 1) / ft);
-  if (blocks > 2147483647LL) throw Failure("invert: too many frame tiles for one launch");
   auto kernel = use_pow2 ? istft_frames_kernel<Tz, Tacc, true> : istft_frames_kernel<Tz, Tacc, false>;
-  const size_t lds = lds_bytes(ft, use_pow2);
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-  SMX_HIP_CHECK(hipGetLastError());
-  (void)job;
+  launch_tiles("invert", kernel, a.lead * ((a.count + ft - 1) / ft), 256, lds_bytes(ft, use_pow2), stream, a);
+}
+
+// The frames kernel of a synthesis whose overlap-add is a launch of its own, one decision per request (DESIGN.md 4.6's route table):
+// Tz = float, S = float: complex64 spectra, float32 interior; Tz = float, S = double: complex64 under the float64 interior; Tz = S = double:
+// complex128
+template <typename Tz, typename S>
+void launch_frames_any(const IstftArgs &a, const StftTables &t, hipStream_t stream) {
+  static const bool mixed_off = env_flag("SMX_MIXED_OFF") == 1;
+  const bool stockham_size = a.fft == 512 || a.fft == 1024 || a.fft == 2048 || a.fft == 4096;
+  if (stockham_size && !fast_path_disabled() && !(sizeof(S) == 8 && diag_flag("SMX_ISTFT_RADIX2") == 1)) return launch_stockham_frames_any<Tz, S>(a, t, stream);
+  if (t.mixed_npass > 0 && !a.mag && !a.unit && !mixed_off) return launch_mixed_frames_any<Tz, S>(a, t, stream);
+  launch_frames<Tz, S>(a, stream);
 }
 
 }  // namespace
@@ -933,8 +897,12 @@ void launch_istft(const IstftJob &job) {
   const double *d_env = env.dev;
   const int64_t head_n = env.head_n, stop = job.env_open ? (int64_t(1) << 60) : env.stop;
   const int64_t left = job.left >= 0 ? job.left : c.left_width();
-  // fused path: fft 2048, hop 512, complex64 spectrum, float32 interior
-  if (istft_fused_2048(job) && diag_flag("SMX_ISTFT_NEW2048") != 1) {
+  // One decision per request, in the order of DESIGN.md 4.6's route table; each condition is a property of the request.
+  const int64_t need = std::max<int64_t>(span, left + job.out_len);   // padded positions the output can ask for
+  // fft 2048, hop 512, complex64 spectrum, float32 interior: the hand-laid kernels (frames + overlap-add + envelope in one launch)
+  const int64_t tiles13 = (need + 512 * kSynHops - 1) / (512 * kSynHops);
+  const bool pipeline = env_flag("SMX_INVERT_PIPELINE") != 0 && job.frames < (int64_t(1) << 23);
+  if (istft_fused_2048(job) && diag_flag("SMX_ISTFT_NEW2048") != 1 && (pipeline || job.lead * tiles13 <= 0x7ffffff0)) {
     SynArgs sa{};
     sa.mag = reinterpret_cast<const float *>(job.mag);
     sa.unit = job.unit ? 1 : 0;
@@ -948,10 +916,7 @@ void launch_istft(const IstftJob &job) {
     sa.left = left;
     sa.env_q0 = job.env_q0;
     sa.span = span;
-    // tiles cover padded positions [0, 512 * 13 * tiles): everything the output can ask for
-    const int64_t need = std::max<int64_t>(span, sa.left + job.out_len);
-    const int64_t tiles = (need + 512 * kSynHops - 1) / (512 * kSynHops);
-    sa.tiles_per_clip = (int)tiles;
+    sa.tiles_per_clip = (int)tiles13;   // tiles cover padded positions [0, 512 * 13 * tiles): everything the output can ask for
     sa.w_m = t.fast_w_m;
     sa.w_n = t.fast_w_n;
     sa.synth_window = t.fast_synth_window;
@@ -960,11 +925,9 @@ void launch_istft(const IstftJob &job) {
     sa.env_tail = d_env + env.head + env.period;
     sa.head = head_n;
     sa.stop = stop;
-    // Round 5: the persistent pipeline kernel (istft_pipe32.hpp) takes every synthesis of this geometry, whatever its size
-    // (Griffin-Lim's factors included), so that a position has one value however the frames reach the kernel (offline,
-    // streaming chunks).
-    // SMX_INVERT_PIPELINE=0: the one-tile-per-workgroup kernel of rounds 1-4 (tests, A/B timing).
-    if (env_flag("SMX_INVERT_PIPELINE") != 0 && job.frames < (int64_t(1) << 23)) {
+    if (pipeline) {
+      // The persistent pipeline kernel (istft_pipe32.hpp) takes every synthesis of this geometry, whatever its size (Griffin-Lim's
+      // factors included), so that a position has one value however the frames reach the kernel (offline, streaming chunks).
       PipeArgs pa{};
       pa.s = sa;
       const int64_t tiles16 = (need + 512 * kIpFT - 1) / (512 * kIpFT);
@@ -979,27 +942,20 @@ void launch_istft(const IstftJob &job) {
       pa.fm_clip = job.fm_pitch * job.fm_rows;
       auto kp = job.fm_pitch > 0 ? ((job.mag || job.unit) ? istft2048_pipe_kernel<true, true> : istft2048_pipe_kernel<false, true>)
                                  : ((job.mag || job.unit) ? istft2048_pipe_kernel<true> : istft2048_pipe_kernel<false>);
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIpLds));
-      SMX_LAUNCH(kp, dim3((unsigned)pa.blocks), dim3(512), kIpLds, job.stream, pa);
-      SMX_HIP_CHECK(hipGetLastError());
-      return;
+      return launch_tiles("invert", kp, pa.blocks, 512, kIpLds, job.stream, pa);
     }
-    const int64_t blocks = job.lead * tiles;
-    if (blocks <= 0x7ffffff0) {
-      const bool linear = diag_flag("SMX_ISTFT_LINEAR") == 1;
-      sa.blocks = blocks;
-      sa.per_xcd = linear ? 0 : (blocks + 7) / 8;
-      const int64_t launched = sa.per_xcd > 0 ? sa.per_xcd * 8 : blocks;
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(istft2048_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSynLds));
-      SMX_LAUNCH(istft2048_kernel, dim3((unsigned)launched), dim3(1024), kSynLds, job.stream, sa);
-      SMX_HIP_CHECK(hipGetLastError());
-      return;
-    }
+    // SMX_INVERT_PIPELINE=0 (tests, A/B timing), or 2^23 frames and more: one 13-hop tile per workgroup, the tiles dealt out XCD by XCD
+    const bool linear = diag_flag("SMX_ISTFT_LINEAR") == 1;
+    sa.blocks = job.lead * tiles13;
+    sa.per_xcd = linear ? 0 : (sa.blocks + 7) / 8;
+    return launch_tiles("invert", istft2048_kernel, sa.per_xcd > 0 ? sa.per_xcd * 8 : sa.blocks, 1024, kSynLds, job.stream, sa);
   }
   // float32, fft 512 / 1024 / 2048 advanced by a quarter or a half of the size: frames + overlap-add fused, no scratch array
-  if (!f64 && job.z_bytes == 8 && (hop * 4 == fft || hop * 2 == fft) && (fft == 512 || fft == 1024 || fft == 2048) && istft_takes_factors(job) &&
-      diag_flag("SMX_ISTFT_UNFUSED") != 1) {
+  const bool quarter = hop * 4 == fft;
+  const int64_t adv = quarter ? 13 : 15;      // complete hops per 16-frame tile
+  const int64_t fused_tiles = (need + hop * adv - 1) / (hop * adv);
+  if (!f64 && job.z_bytes == 8 && (quarter || hop * 2 == fft) && (fft == 512 || fft == 1024 || fft == 2048) && istft_takes_factors(job) &&
+      diag_flag("SMX_ISTFT_UNFUSED") != 1 && job.lead * fused_tiles <= 2147483647LL) {
     IstftArgs fa{};
     fa.z = job.z;
     fa.lead = job.lead;
@@ -1024,15 +980,14 @@ void launch_istft(const IstftJob &job) {
     o.env_period = d_env + env.head;
     o.env_tail = d_env + env.head + env.period;
     o.env_rperiod = d_env + env.head + env.period + env.tail;
-    const int64_t need = std::max<int64_t>(span, o.left + job.out_len);
-    const int64_t adv = hop * 4 == fft ? 13 : 15;      // complete hops per 16-frame tile
-    o.tiles_per_clip = (int)((need + hop * adv - 1) / (hop * adv));
-    const bool quarter = hop * 4 == fft;
-    const bool done = fft == 512 ? (quarter ? launch_stockham_fused<9, 4>(fa, t, o, job.stream) : launch_stockham_fused<9, 2>(fa, t, o, job.stream))
-                    : fft == 1024 ? (quarter ? launch_stockham_fused<10, 4>(fa, t, o, job.stream) : launch_stockham_fused<10, 2>(fa, t, o, job.stream))
-                                  : (quarter ? launch_stockham_fused<11, 4>(fa, t, o, job.stream) : launch_stockham_fused<11, 2>(fa, t, o, job.stream));
-    if (done) return;
+    o.tiles_per_clip = (int)fused_tiles;
+    switch (fft) {
+      case 512: return quarter ? launch_stockham_fused<9, 4>(fa, t, o, job.stream) : launch_stockham_fused<9, 2>(fa, t, o, job.stream);
+      case 1024: return quarter ? launch_stockham_fused<10, 4>(fa, t, o, job.stream) : launch_stockham_fused<10, 2>(fa, t, o, job.stream);
+      default: return quarter ? launch_stockham_fused<11, 4>(fa, t, o, job.stream) : launch_stockham_fused<11, 2>(fa, t, o, job.stream);
+    }
   }
+  // everything else: the windowed frames y through a scratch array, then the overlap-add
   // clips in chunks so that the windowed frames y stay within ~1 GiB
   const size_t acc_bytes = f64 ? 8 : 4;
   const size_t per_clip = (size_t)count * (size_t)fft * acc_bytes;
@@ -1060,14 +1015,9 @@ void launch_istft(const IstftJob &job) {
     fa.prev = job.prev ? reinterpret_cast<const float2 *>(job.prev) + c0 * c.bins() * job.frames : nullptr;
     fa.beta = (float)job.beta;
     fa.unit = job.unit ? 1 : 0;
-    if (job.z_bytes == 16) {
-      if (!launch_stockham_frames_wide_any<double>(fa, t, job.stream) && !launch_mixed_frames_any<double, double>(fa, t, job.stream))
-        launch_frames<double, double>(job, fa, job.stream);
-    } else if (f64) {
-      if (!launch_stockham_frames_wide_any<float>(fa, t, job.stream) && !launch_mixed_frames_any<float, double>(fa, t, job.stream))
-        launch_frames<float, double>(job, fa, job.stream);
-    }
-    else if (!launch_stockham_frames_any(fa, t, job.stream) && !launch_mixed_frames_any<float, float>(fa, t, job.stream)) launch_frames<float, float>(job, fa, job.stream);
+    if (job.z_bytes == 16) launch_frames_any<double, double>(fa, t, job.stream);
+    else if (f64) launch_frames_any<float, double>(fa, t, job.stream);
+    else launch_frames_any<float, float>(fa, t, job.stream);
     OlaArgs oa{};
     oa.y = d_y;
     oa.out = reinterpret_cast<unsigned char *>(job.out) + c0 * job.out_len * elem_out;

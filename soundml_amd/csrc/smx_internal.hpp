@@ -81,6 +81,16 @@ extern std::atomic<unsigned long long> g_kernel_launches;
     hipLaunchKernelGGL(__VA_ARGS__);                                          \
   } while (0)
 
+// One launch of `blocks` workgroups of a frame-tile kernel with `lds` bytes of dynamic LDS (past the 64 KB a kernel gets unasked);
+// `what` names the entry point in the error ("stft", "invert")
+template <typename K, typename... Args>
+void launch_tiles(const char *what, K kernel, int64_t blocks, int threads, size_t lds, hipStream_t stream, const Args &...args) {
+  if (blocks > 2147483647LL) throw Failure(format("%s: too many frame tiles for one launch", what));
+  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(threads), lds, stream, args...);
+  SMX_HIP_CHECK(hipGetLastError());
+}
+
 // ---- device-resident tables owned by a config, one set per HIP device ------
 struct DeviceBuffer {
   void *ptr = nullptr;
@@ -94,20 +104,19 @@ struct StftTables {
   // generic pow2 kernel: exp(-2 pi i j / N), j < N/2 ; direct DFT kernel: j < N
   double2 *twiddle_f64 = nullptr;
   float2 *twiddle_f32 = nullptr;
-  int64_t twiddle_len = 0;
   // fast kernels (N = 2048 family): half-scaled window + split twiddle tables
   float *fast_window = nullptr;    // 0.5 * window, f32
   float2 *fast_w_m = nullptr;      // exp(-2 pi i j / M), j < M   (M = N/2)
   double2 *fast_w_m_f64 = nullptr; // the same in float64 (float64-interior Stockham form, fft 512 .. 4096)
   float2 *fast_w_n = nullptr;      // exp(-2 pi i k / N), k <= M
-  // chirp-z (Bluestein) path of the generic float32 kernels for sizes that are not powers of two: an N-point DFT
+  // chirp-z (Bluestein) path of the generic float32 kernels for odd sizes: an N-point DFT
   // as one circular convolution of length blu_m = 2^blu_log2m >= 2 N - 1
   float2 *blu_chirp = nullptr;     // exp(-i pi n^2 / N) * window[n], n < N   (window folded in)
   float2 *blu_post = nullptr;      // exp(-i pi k^2 / N), k < N
   float2 *blu_filter = nullptr;    // FFT_M of exp(+i pi m^2 / N) (wrapped), times 1/M, natural order
   float2 *blu_tw = nullptr;        // exp(-2 pi i j / M), j < M/2
   int blu_log2m = 0;
-  // even sizes: chirp-z of length L = N/2 over (even, odd) sample pairs + the real-input post-pass
+  // even sizes that are not powers of two: chirp-z of length L = N/2 over (even, odd) sample pairs + the real-input post-pass
   float2 *blu2_chirp = nullptr;    // exp(-i pi n^2 / L), n < L (input chirp and post factor)
   float2 *blu2_filter = nullptr;   // FFT_M2 of exp(+i pi m^2 / L) (wrapped), times 1/M2
   float2 *blu2_tw = nullptr;       // exp(-2 pi i j / M2), j < M2/2

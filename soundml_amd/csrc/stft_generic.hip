@@ -1,22 +1,23 @@
 // STFT kernels for every geometry the fused fft-2048 kernels of stft_fast.hip do not serve: any fft_size, hop,
 // alignment and pad mode, float32 or float64 audio, float32 or float64 interior (reference semantics for every
-// Stft.Config, stft.ml:356-364 + :670-674).  In the order the dispatcher (launch_stft_generic, at the end) prefers them:
+// Stft.Config, stft.ml:356-364 + :670-674).  launch_stft_generic, at the end, picks ONE of them per request; DESIGN.md 4.3
+// has the route table (request -> kernel instantiation, with the smallest request that reaches each).
 //
-//   stft_stockham_power16_kernel     fft 512 .. 8192, power output (and, MEL, the fused mel / projection tail): FT
+//   stft_stockham_power16_kernel     fft 512 .. 8192, power output (and, MEL, the fused mel tail at fft 512 / 1024): FT
 //                                    frames per workgroup on the Stockham passes of fft_device.hpp, real form
 //                                    (one half-size complex transform + post-pass), NO stage: each frame's column
 //                                    returns into its own work buffer and leaves through columns_out; float32, or
-//                                    double for the float64 interior;
+//                                    double for the float64 interior (fft 512 .. 4096);
 //   stft_stockham_complex16_kernel   the same for complex output (X[M] packed with X[0], XOR-placed columns);
-//   stft_bluestein_power16_kernel    even sizes up to 1024 that are not powers of two (fft 400 ...): chirp-z of
-//                                    length N/2 on the same passes, same column tail;
-//   stft_stockham_real_kernel        the staged form ([bins][FT + 1] stage in LDS) for what is left of fft 512 ..
-//   stft_stockham_kernel             16384 (full-size complex form for fft 256 and from 4096 on);
-//   stft_bluestein_real_kernel /     chirp-z, half length for even sizes, full length for odd ones, up to fft 8192;
-//   stft_bluestein_kernel
-//   stft_generic_kernel              everything else: radix-2 passes in LDS (power of two) or a direct DFT against an
-//                                    N-entry float64-built table, float32 or float64, FT frames staged and written
-//                                    frames-fastest.
+//   stft2048_power_wide_kernel       (stft_wide_p64.hpp) fft 2048, float32 audio, float64 interior, power: persistent workgroups;
+//   stft_stockham_kernel             fft 256 and 16384: full-size complex form, [bins][FT + 1] stage in LDS (16384: none);
+//   stft_mixed_power16_kernel        N / 2 (even N) or N (odd N) = 2^a 3^b 5^c 7^d <= 1024: direct mixed-radix transform, either interior;
+//   stft_bluestein_power16_kernel    the other even sizes up to 1024, power / mel: chirp-z of length N/2, same column tail;
+//   stft_bluestein_real_kernel /     chirp-z with the staged tail: half length for even sizes, full length for odd ones,
+//   stft_bluestein_kernel            up to fft 8192;
+//   stft_generic_kernel              everything else, and everything under SMX_DISABLE_FAST: radix-2 passes in LDS (power
+//                                    of two) or a direct DFT against an N-entry float64-built table, float32 or float64,
+//                                    FT frames staged and written frames-fastest.
 #include <cstdlib>
 
 #include "fft_device.hpp"
@@ -45,6 +46,17 @@ struct GenericArgs {
   int log2n;   // >= 0 for the power-of-two kernel
   int ft;      // frames per workgroup
   int direct;  // Stockham kernel: results go straight from registers to memory (no room for an LDS stage)
+
+  GenericArgs() = default;
+  // the request; window and twiddle are the interior's plain tables (a launcher whose kernel wants another window sets it)
+  GenericArgs(const StftJob &job, const StftTables &t)
+      : x(job.x), n(job.n), x_stride(job.x_stride), lead(job.lead), fft(job.cfg->fft_size), hop(job.cfg->hop), left(job.left), pad(job.pad),
+        pad_value(job.pad_value), p0(job.p0), count(job.count), mode((int)job.mode), power(job.power), out(job.out), out_stride(job.out_stride),
+        out_offset(job.out_offset), bins(job.cfg->bins()), log2n(0), ft(0), direct(0) {
+    const bool wide = job.in_bytes == 8 || job.interior == SMX_INTERIOR_F64;
+    window = wide ? (const void *)t.window_f64 : (const void *)t.window_f32;
+    twiddle = wide ? (const void *)t.twiddle_f64 : (const void *)t.twiddle_f32;
+  }
 };
 
 // two neighbouring samples as one access; only element alignment is promised (frames start anywhere)
@@ -237,7 +249,7 @@ __device__ __forceinline__ void flush_stage(const GenericArgs &a, const unsigned
   }
 }
 
-// ---- power-of-two sizes 1024 .. 16384, float32 interior: Stockham passes of fft_device.hpp ---------------------
+// ---- fft 256 and 16384, float32 interior: Stockham passes of fft_device.hpp ------------------------------------
 // N/16 threads own one frame (16 points each in registers, 3-4 LDS round trips instead of log2 N radix-2 passes);
 // a workgroup of >= 256 threads transforms G = 256 / (N/16) frames at a time (one for N >= 4096) and FT frames in
 // all, staged in LDS and written frames-fastest like the kernels above.  The frame is transformed as a complex
@@ -315,194 +327,38 @@ __global__ void __launch_bounds__((1 << LOG2N) / 16 < 256 ? 256 : (1 << LOG2N) /
   flush_stage<float>(a, stage, clip, f0, nf);
 }
 
-template <int LOG2N>
-bool launch_stockham(const StftJob &job, GenericArgs a) {
-  constexpr int N = 1 << LOG2N, T = N / 16, G = T < 256 ? 256 / T : 1, THREADS = T < 256 ? 256 : T;
+// The launch of a staged float32 kernel (stft_stockham_kernel, the two chirp-z ones): G frames transform at a time in `work` bytes
+// of buffers, and the [bins][ft + 1] stage takes the LDS that is left -- ft = 16, 8 ... G frames per workgroup; where not even G
+// columns fit (fft 16384: the work buffer alone is 128 KB) the results go straight from registers to memory (direct).
+template <typename K, typename... Args>
+void launch_staged(K kernel, const StftJob &job, GenericArgs a, int G, int threads, size_t work, const Args &...args) {
   const size_t elem_out = (job.mode == OUT_COMPLEX ? 2 : 1) * sizeof(float);
-  const size_t work = (size_t)G * N * sizeof(float2);
-  auto stage_bytes = [&](int ft) { return (size_t)a.bins * (size_t)(ft + 1) * elem_out + 16; };
-  int ft = 16;
-  while (ft > G && work + stage_bytes(ft) > kLdsLimit) ft >>= 1;
-  a.direct = work + stage_bytes(ft) > kLdsLimit ? 1 : 0;   // fft 16384: the work buffer alone is 128 KB
-  if (a.direct) ft = G;
-  if (work > kLdsLimit) return false;
-  a.ft = ft;
-  const int64_t blocks = a.lead * ((a.count + ft - 1) / ft);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = a.direct ? work : work + stage_bytes(ft);
-  auto kernel = stft_stockham_kernel<LOG2N, float>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
-}
-
-// ---- power-of-two sizes 512 .. 16384, float32 interior: the frame as ONE half-size complex transform ----------
-// z[i] = x[2i] w[2i] + i x[2i+1] w[2i+1] (M = N/2 points, the window pre-halved), Z = FFT_M(z), then
-//   X[k] = (Z[k] + conj Z[M-k]) - i W_N^k (Z[k] - conj Z[M-k]),  X[M] = Re Z[0] - Im Z[0]
-// -- half the passes' work of the kernel above for one more LDS round trip (the partner Z[M-k] lives in another
-// thread).  M/16 threads own a frame; transforms of at most 64 threads are wave-private (no workgroup barriers).
-// S = double: the reference's float64 interior (float32 or float64 audio, results rounded once to Tout) on the same
-// passes, fft 512 .. 4096 (16 complex doubles per thread need the 256-register budget of a 256-thread workgroup).
-template <int LOG2N, typename Tin, typename S, typename Tout>
-__global__ void __launch_bounds__((1 << LOG2N) / 32 < 256 ? 256 : (1 << LOG2N) / 32)
-    stft_stockham_real_kernel(GenericArgs a, const typename fftdev::vec2_of<S>::type *tw_m,
-                              const typename fftdev::vec2_of<S>::type *tw_n) {
-  using namespace fftdev;
-  using V = typename vec2_of<S>::type;
-  using CO = typename Vec2<Tout>::type;
-  constexpr int N = 1 << LOG2N, LOG2M = LOG2N - 1, M = N / 2, T = M / 16, G = T < 256 ? 256 / T : 1;
-  constexpr bool WAVE = T <= 64;
-  constexpr int RL = LastPass<LOG2M>::R, NSL = LastPass<LOG2M>::NS, GL = 16 / RL;
-  // float32: the window table is pre-halved; float64: the config's own window, halved here (exact either way)
-  constexpr S kHalf = sizeof(S) == 8 ? (S)0.5 : (S)1.0;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  V *work = reinterpret_cast<V *>(smem);                                 // G buffers of M complex
-  unsigned char *stage = smem + (size_t)G * M * sizeof(V);
-  const int ft = a.ft, sstride = ft + 1;
-  const int64_t tiles = (a.count + ft - 1) / ft;
-  const int64_t clip = blockIdx.x / tiles, tile = blockIdx.x % tiles;
-  const Tin *x = reinterpret_cast<const Tin *>(a.x) + clip * a.x_stride;
-  const S *window = reinterpret_cast<const S *>(a.window);
-  const int64_t bins = a.bins;
-  const int tid = threadIdx.x % T, grp = threadIdx.x / T;
-  V *z = work + (size_t)grp * M;
-  const int64_t f0 = tile * ft;
-  const int nf = (int)((a.count - f0) < ft ? (a.count - f0) : ft);
-  auto emit = [&](int f, int k, S re, S im) {
-    if (a.direct) {
-      const int64_t o = clip * bins * a.out_stride + a.out_offset + f0 + f + (int64_t)k * a.out_stride;
-      if (a.mode == OUT_COMPLEX) {
-        CO c;
-        c.x = (Tout)re;
-        c.y = (Tout)im;
-        reinterpret_cast<CO *>(a.out)[o] = c;
-      } else {
-        reinterpret_cast<Tout *>(a.out)[o] = magnitude_pow<S, Tout>(re, im, a.power);
-      }
-    } else if (a.mode == OUT_COMPLEX) {
-      CO c;
-      c.x = (Tout)re;
-      c.y = (Tout)im;
-      reinterpret_cast<CO *>(stage)[k * sstride + f] = c;
-    } else {
-      reinterpret_cast<Tout *>(stage)[k * sstride + f] = magnitude_pow<S, Tout>(re, im, a.power);
-    }
-  };
-  for (int fb = 0; fb < nf; fb += G) {
-    const int f = fb + grp;
-    const bool have = f < nf;                          // uniform per group of T threads
-    cpx<S> r[16];
-    if (have) {
-      const int64_t s0 = (a.p0 + f0 + f) * a.hop - a.left;
-      if (s0 >= 0 && s0 + N <= a.n) {   // the frame lies inside the signal (uniform per group): plain loads
-        const Tin *xs = x + s0;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          const int i = 2 * (tid + T * m);
-          // one 8-byte access for the two samples (element-aligned only) and one for their window values
-        const auto xv = *reinterpret_cast<const typename Pair<Tin>::type *>(xs + i);
-        const V wv = reinterpret_cast<const V *>(window)[tid + T * m];
-        r[m] = {(S)xv.x * wv.x * kHalf, (S)xv.y * wv.y * kHalf};
-        }
-      } else {
-#pragma unroll 1
-        for (int m = 0; m < 16; ++m) {
-          const int i = 2 * (tid + T * m);
-          const S v0 = (S)fetch_sample<Tin>(x, a.n, s0 + i, a.pad, a.pad_value) * window[i] * kHalf;
-          const S v1 = (S)fetch_sample<Tin>(x, a.n, s0 + i + 1, a.pad, a.pad_value) * window[i + 1] * kHalf;
-#pragma unroll
-          for (int mm = 0; mm < 16; ++mm)
-            if (mm == m) r[mm] = {v0, v1};
-        }
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) r[m] = {(S)0, (S)0};
-    }
-    fft_passes<LOG2M, true, WAVE>(r, z, tid, tw_m);
-    // the last pass left its results in registers (its reads of z are behind a sync): Z in natural order
-#pragma unroll
-    for (int i = 0; i < GL; ++i)
-#pragma unroll
-      for (int j = 0; j < RL; ++j) {
-        V o;
-        o.x = r[i * RL + j].x;
-        o.y = r[i * RL + j].y;
-        z[swz(out_index<RL, NSL, T>(tid, i, j))] = o;
-      }
-    stockham_sync<WAVE>();
-    if (have) {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const int k = tid + T * m;
-        const V zk = z[swz(k)], zm = z[swz((M - k) & (M - 1))];
-        const S er = zk.x + zm.x, ei = zk.y - zm.y;            // Z[k] + conj Z[M-k]
-        const S dr = zk.x - zm.x, di = zk.y + zm.y;            // Z[k] - conj Z[M-k]
-        const V w = tw_n[k];                                   // exp(-2 pi i k / N)
-        // -i w d = -i (w.x + i w.y)(dr + i di) = (w.x di + w.y dr) - i (w.x dr - w.y di)
-        emit(f, k, er + (w.x * di + w.y * dr), ei - (w.x * dr - w.y * di));
-      }
-      if (tid == 0) {
-        const V z0 = z[swz(0)];
-        emit(f, M, (S)2 * (z0.x - z0.y), (S)0);
-      }
-    }
-    __syncthreads();   // the next round's first pass writes the work buffers again
-  }
-  if (a.direct) return;
-  flush_stage<Tout>(a, stage, clip, f0, nf);
-}
-
-template <int LOG2N, typename Tin, typename S, typename Tout>
-bool launch_stockham_real(const StftJob &job, GenericArgs a, const StftTables &t) {
-  using V = typename fftdev::vec2_of<S>::type;
-  constexpr int N = 1 << LOG2N, M = N / 2, T = M / 16, G = T < 256 ? 256 / T : 1, THREADS = T < 256 ? 256 : T;
-  constexpr bool wide = sizeof(S) == 8;
-  static_assert(!wide || THREADS == 256, "the float64 form needs the register budget of a 256-thread workgroup");
-  const void *tw_m = wide ? (const void *)t.fast_w_m_f64 : (const void *)t.fast_w_m;
-  const void *tw_n = wide ? (const void *)t.twiddle_f64 : (const void *)t.fast_w_n;
-  const void *window = wide ? (const void *)t.window_f64 : (const void *)t.fast_window;
-  if (!window || !tw_m || !tw_n) return false;
-  const size_t elem_out = (job.mode == OUT_COMPLEX ? 2 : 1) * sizeof(Tout);
-  const size_t work = (size_t)G * M * sizeof(V);
   auto stage_bytes = [&](int ft) { return (size_t)a.bins * (size_t)(ft + 1) * elem_out + 16; };
   int ft = 16;
   while (ft > G && work + stage_bytes(ft) > kLdsLimit) ft >>= 1;
   a.direct = work + stage_bytes(ft) > kLdsLimit ? 1 : 0;
   if (a.direct) ft = G;
-  if (work > kLdsLimit) return false;
   a.ft = ft;
-  a.window = window;
-  const int64_t blocks = a.lead * ((a.count + ft - 1) / ft);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = a.direct ? work : work + stage_bytes(ft);
-  auto kernel = stft_stockham_real_kernel<LOG2N, Tin, S, Tout>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, (const V *)tw_m, (const V *)tw_n);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
+  launch_tiles("stft", kernel, a.lead * ((a.count + ft - 1) / ft), threads, a.direct ? work : work + stage_bytes(ft), job.stream, a, args...);
 }
 
-// the float64-interior form for one (audio, output) dtype pair: fft 512 .. 4096
-template <typename Tin, typename Tout>
-bool launch_stockham_wide(const StftJob &job, const GenericArgs &a, const StftTables &t, int64_t fft) {
-  switch (fft) {
-    case 512: return launch_stockham_real<9, Tin, double, Tout>(job, a, t);
-    case 1024: return launch_stockham_real<10, Tin, double, Tout>(job, a, t);
-    case 2048: return launch_stockham_real<11, Tin, double, Tout>(job, a, t);
-    case 4096: return launch_stockham_real<12, Tin, double, Tout>(job, a, t);
-    default: return false;
-  }
+template <int LOG2N>
+void launch_stockham(const StftJob &job, const GenericArgs &a) {
+  constexpr int N = 1 << LOG2N, T = N / 16, G = T < 256 ? 256 / T : 1, THREADS = T < 256 ? 256 : T;
+  static_assert((size_t)G * N * sizeof(float2) <= kLdsLimit, "the work buffers fit the LDS");
+  launch_staged(stft_stockham_kernel<LOG2N, float>, job, a, G, THREADS, (size_t)G * N * sizeof(float2));
 }
 
-// ---- fft 512 / 1024, float32, power output: 16 frames per workgroup with NO separate stage ----------------------
-// The kernel above keeps a [bins][17] stage next to its work buffers, which leaves two 4-wave workgroups per CU at
-// fft 1024.  Here a workgroup owns 16 frames at once (16 x M/16 threads), and after the post-pass each frame's
+// ---- power-of-two sizes 512 .. 8192, power output: FT frames per workgroup with NO separate stage ----------------
+// The frame as ONE half-size complex transform: z[i] = x[2i] w[2i] + i x[2i+1] w[2i+1] (M = N/2 points, the float32 window
+// pre-halved), Z = FFT_M(z), then
+//   X[k] = (Z[k] + conj Z[M-k]) - i W_N^k (Z[k] - conj Z[M-k]),  X[M] = Re Z[0] - Im Z[0].
+// A workgroup owns FT frames at once (FT x M/16 threads), and after the post-pass each frame's
 // |X|^p column goes back into that frame's own, now dead, work buffer (M + 1 floats in the room of M complex),
 // rotated by 2 f floats so that the flush -- 16 frames of one bin per 16 lanes -- reads 32 distinct banks per
 // half-wave.  LDS is the work buffers alone: 32 KB (fft 512, five workgroups per CU) / 64 KB (fft 1024, two
 // 8-wave workgroups).  Transforms are wave-private (at most 32 threads each): one workgroup barrier in all.
+// S = double: the reference's float64 interior (float32 or float64 audio, results rounded once to Tout), fft 512 .. 4096.
 // MEL: the 16 power columns never leave the chip: W (banded, zero-padded float32 image of the float64 filterbank) x
 // columns on v_mfma_f32_16x16x4_f32, one 16-row tile of W per wave at a time over the tile's own band of bins, and
 // the [n_mels; 16 frames] block goes out as 64-byte row runs (Soundml.mel_spectrogram for fft 512 / 1024).
@@ -778,34 +634,6 @@ __global__ void __launch_bounds__(FT * ((1 << LOG2N) / 32)) stft_stockham_power1
                                                                    MEL ? reinterpret_cast<float *>(smem + (size_t)FT * M * sizeof(V)) : nullptr);
 }
 
-template <int LOG2N, int FT = 16>
-bool launch_stockham_power16(const StftJob &job, GenericArgs a, const StftTables &t, const MelTail *mel = nullptr) {
-  constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);   // FT frames x M/16 threads
-  if (!t.fast_window || !t.fast_w_m || !t.fast_w_n) return false;
-  a.window = t.fast_window;
-  const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = (size_t)FT * M * sizeof(float2);
-  if constexpr (FT == 16) {
-    if (mel) {
-      const size_t lds_mel = lds + (size_t)(THREADS / 64) * 1024;   // the helper waves' partial tiles (columns_out)
-      auto kernel = stft_stockham_power16_kernel<LOG2N, float, true, 16>;
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mel));
-      SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds_mel, job.stream, a, (const float2 *)t.fast_w_m,
-                         (const float2 *)t.fast_w_n, *mel);
-      SMX_HIP_CHECK(hipGetLastError());
-      return true;
-    }
-  }
-  if (mel) return false;
-  auto kernel = stft_stockham_power16_kernel<LOG2N, float, false, FT>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, (const float2 *)t.fast_w_m,
-                     (const float2 *)t.fast_w_n, MelTail{});
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
-}
-
 // ---- fft 512 / 1024, float32, complex output: the same stage-free scheme for Stft.transform ---------------------
 // A frame's spectrum is M + 1 complex values, one more than its work buffer holds -- but X[0] and X[M] are both real,
 // so X[M] rides in the imaginary slot of X[0].  There is no spare room to rotate the columns; position k of frame f
@@ -928,84 +756,35 @@ __global__ void __launch_bounds__(FT * ((1 << LOG2N) / 32)) stft_stockham_comple
   }
 }
 
-template <int LOG2N, int FT = 16>
-bool launch_stockham_complex16(const StftJob &job, GenericArgs a, const StftTables &t) {
-  constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);
-  if (!t.fast_window || !t.fast_w_m || !t.fast_w_n) return false;
-  a.window = t.fast_window;
-  const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = (size_t)FT * M * sizeof(float2);
-  auto kernel = stft_stockham_complex16_kernel<LOG2N, float, FT>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, (const float2 *)t.fast_w_m, (const float2 *)t.fast_w_n);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
-}
-
-// the float64 interior, complex output: float32 audio -> complex64, float64 audio -> complex128
-template <int LOG2N, int FT, typename Tio>
-bool launch_stockham_complex16_wide(const StftJob &job, GenericArgs a, const StftTables &t) {
-  constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);
-  static_assert(THREADS <= 512, "16 complex doubles per thread need the 256-register budget");
-  if (!t.window_f64 || !t.fast_w_m_f64 || !t.twiddle_f64) return false;
-  a.window = t.window_f64;
-  const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = (size_t)FT * M * sizeof(double2);
-  auto kernel = stft_stockham_complex16_kernel<LOG2N, Tio, FT, double, Tio>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, (const double2 *)t.fast_w_m_f64,
-                     (const double2 *)t.twiddle_f64);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
-}
-
-template <typename Tio>
-bool launch_stockham_complex16_wide_any(const StftJob &job, const GenericArgs &a, const StftTables &t, int64_t fft) {
-  switch (fft) {
-    case 512: return launch_stockham_complex16_wide<9, 16, Tio>(job, a, t);
-    case 1024: return launch_stockham_complex16_wide<10, 16, Tio>(job, a, t);
-    case 2048: return launch_stockham_complex16_wide<11, 8, Tio>(job, a, t);
-    case 4096: return launch_stockham_complex16_wide<12, 4, Tio>(job, a, t);
-    default: return false;
+// the launch of either kernel: S = float (float32 audio; mel: the fused tail, fft 512 / 1024 only) or S = double (the float64
+// interior: Tio = float, float32 audio -> float32 / complex64, or Tio = double, float64 audio -> float64 / complex128)
+template <int LOG2N, int FT, typename S = float, typename Tio = float>
+void launch_stockham16(const StftJob &job, GenericArgs a, const StftTables &t, const MelTail *mel = nullptr) {
+  using V = typename fftdev::vec2_of<S>::type;
+  constexpr bool wide = sizeof(S) == 8;
+  constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);   // FT frames x M/16 threads
+  static_assert(!wide || THREADS <= 512, "16 complex doubles per thread need the 256-register budget");
+  const V *tw_m, *tw_n;
+  if constexpr (wide) {
+    a.window = t.window_f64;
+    tw_m = t.fast_w_m_f64;
+    tw_n = t.twiddle_f64;
+  } else {
+    a.window = t.fast_window;
+    tw_m = t.fast_w_m;
+    tw_n = t.fast_w_n;
   }
-}
-
-// the float64 interior, power output: the stage-free kernel on doubles (FT frames of M double2), float32 audio with
-// float32 columns or float64 audio with float64 ones
-template <int LOG2N, int FT, typename Tio>
-bool launch_stockham_power16_wide(const StftJob &job, GenericArgs a, const StftTables &t) {
-  constexpr int M = (1 << LOG2N) / 2, THREADS = FT * (M / 16);
-  static_assert(THREADS <= 512, "16 complex doubles per thread need the 256-register budget");
-  if (!t.window_f64 || !t.fast_w_m_f64 || !t.twiddle_f64) return false;
-  a.window = t.window_f64;
   const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = (size_t)FT * M * sizeof(double2);
-  auto kernel = stft_stockham_power16_kernel<LOG2N, Tio, false, FT, double, Tio>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, (const double2 *)t.fast_w_m_f64,
-                     (const double2 *)t.twiddle_f64, MelTail{});
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
+  const size_t lds = (size_t)FT * M * sizeof(V);
+  if constexpr (!wide && FT == 16 && LOG2N <= 10) {
+    if (mel)   // + the helper waves' partial tiles (columns_out)
+      return launch_tiles("stft", stft_stockham_power16_kernel<LOG2N, float, true, 16>, blocks, THREADS, lds + (size_t)(THREADS / 64) * 1024, job.stream, a, tw_m, tw_n, *mel);
+  }
+  if (job.mode == OUT_COMPLEX) launch_tiles("stft", stft_stockham_complex16_kernel<LOG2N, Tio, FT, S, Tio>, blocks, THREADS, lds, job.stream, a, tw_m, tw_n);
+  else launch_tiles("stft", stft_stockham_power16_kernel<LOG2N, Tio, false, FT, S, Tio>, blocks, THREADS, lds, job.stream, a, tw_m, tw_n, MelTail{});
 }
 
 #include "stft_wide_p64.hpp"   // fft 2048, float32 audio: the persistent-workgroup form of the same arithmetic
-
-template <typename Tio>
-bool launch_stockham_power16_wide_any(const StftJob &job, const GenericArgs &a, const StftTables &t, int64_t fft) {
-  if constexpr (sizeof(Tio) == 4) {
-    if (fft == 2048 && wide64::launch(job, a, t)) return true;
-  }
-  switch (fft) {
-    case 512: return launch_stockham_power16_wide<9, 16, Tio>(job, a, t);
-    case 1024: return launch_stockham_power16_wide<10, 16, Tio>(job, a, t);
-    case 2048: return launch_stockham_power16_wide<11, 8, Tio>(job, a, t);
-    case 4096: return launch_stockham_power16_wide<12, 4, Tio>(job, a, t);
-    default: return false;
-  }
-}
 
 // ---- any other size up to 8192, float32 interior: chirp-z (Bluestein) on the same Stockham passes ------------
 // X[k] = c_k sum_n (x[n] w[n] c_n) conj(c)_(k-n),  c_n = exp(-i pi n^2 / N): one circular convolution of length
@@ -1290,25 +1069,16 @@ __global__ void __launch_bounds__(1 << LOG2M) stft_bluestein_power16_kernel(Gene
 }
 
 template <int LOG2M>
-bool launch_bluestein_power16(const StftJob &job, GenericArgs a, const StftTables &t, const MelTail *mel) {
+void launch_bluestein_power16(const StftJob &job, GenericArgs a, const StftTables &t, const MelTail *mel) {
   constexpr int M = 1 << LOG2M;
   a.window = t.blu2_window;
   const Blu2Args b{t.blu2_chirp, t.blu2_filter, t.blu2_tw, (const float2 *)t.twiddle_f32};
   const int64_t blocks = a.lead * ((a.count + 15) / 16);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
   const size_t lds = (size_t)16 * M * sizeof(float2);
-  if (mel) {
-    const size_t lds_mel = lds + (size_t)(M / 64) * 1024;   // the helper waves' partial tiles (columns_out)
-    auto kernel = stft_bluestein_power16_kernel<LOG2M, float, true>;
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mel));
-    SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(M), lds_mel, job.stream, a, b, *mel);
-  } else {
-    auto kernel = stft_bluestein_power16_kernel<LOG2M, float, false>;
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(M), lds, job.stream, a, b, MelTail{});
-  }
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
+  if (mel)   // + the helper waves' partial tiles (columns_out)
+    launch_tiles("stft", stft_bluestein_power16_kernel<LOG2M, float, true>, blocks, M, lds + (size_t)(M / 64) * 1024, job.stream, a, b, *mel);
+  else
+    launch_tiles("stft", stft_bluestein_power16_kernel<LOG2M, float, false>, blocks, M, lds, job.stream, a, b, MelTail{});
 }
 
 // ---- even sizes whose half length L = N / 2 is 2^a 3^b 5^c (fft 400, 480, 640, 800, 960, 1000, ...): a direct mixed-radix
@@ -1497,153 +1267,90 @@ __global__ void __launch_bounds__(64 * FT) stft_mixed_power16_kernel(GenericArgs
                                   MEL ? reinterpret_cast<float *>(work + LP) : nullptr, (int)(2 * LP * sizeof(V) / sizeof(float)));
 }
 
-template <int LOG2LP, int FT = 16, bool FULL = false>
-bool launch_mixed_power16(const StftJob &job, GenericArgs a, const StftTables &t, const MixedPlan<float> &pl, const MelTail *mel) {
+// S = float: float32 audio and interior; S = double: the float64 interior on Tio = float (float32 audio, float32 / complex64 out)
+// or double (float64 audio, float64 / complex128 out).  mel: the fused tail (float32, 16 frames, even sizes), which only the diagnostic
+// SMX_MEL16_FUSED selects (launch_mel_spectrogram_16).
+template <int LOG2LP, int FT, bool FULL, typename S, typename Tio>
+void launch_mixed_power16(const StftJob &job, GenericArgs a, const StftTables &t, const MixedPlan<S> &pl, const MelTail *mel) {
+  using V = typename fftdev::vec2_of<S>::type;
   constexpr int LP = 1 << LOG2LP;
-  a.window = FULL ? (const void *)t.window_f32 : (const void *)t.blu2_window;
+  if constexpr (sizeof(S) == 8) a.window = t.window_f64;
+  else a.window = FULL ? (const void *)t.window_f32 : (const void *)t.blu2_window;
   const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = (size_t)FT * 4 * LP * sizeof(float) + (size_t)2 * LP * sizeof(float2);   // frames + the two twiddle tables
-  auto launch = [&](auto kernel, const MelTail &tail) {
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(64 * FT), lds, job.stream, a, pl, tail);
-    SMX_HIP_CHECK(hipGetLastError());
-    return true;
-  };
-  if (job.mode == OUT_COMPLEX) return mel ? false : launch(stft_mixed_power16_kernel<LOG2LP, float, false, FT, true, float, float, FULL>, MelTail{});
-  if constexpr (FT != 16 || FULL) {   // the MFMA tail is 16 frames wide (and the odd sizes have no fused mel face)
-    return mel ? false : launch(stft_mixed_power16_kernel<LOG2LP, float, false, FT, false, float, float, FULL>, MelTail{});
+  const size_t lds = (size_t)(FT + 1) * 2 * LP * sizeof(V);   // the frames' buffer pairs + the two twiddle tables
+  if constexpr (FT == 16 && !FULL && sizeof(S) == 4) {   // (the helper waves' partial tiles live in the frames' second buffers: no LDS beyond lds)
+    if (mel) return launch_tiles("stft", stft_mixed_power16_kernel<LOG2LP, float, true>, blocks, 64 * FT, lds, job.stream, a, pl, *mel);
+  }
+  if (job.mode == OUT_COMPLEX) launch_tiles("stft", stft_mixed_power16_kernel<LOG2LP, Tio, false, FT, true, S, Tio, FULL>, blocks, 64 * FT, lds, job.stream, a, pl, MelTail{});
+  else launch_tiles("stft", stft_mixed_power16_kernel<LOG2LP, Tio, false, FT, false, S, Tio, FULL>, blocks, 64 * FT, lds, job.stream, a, pl, MelTail{});
+}
+
+// a size with a forward mixed-radix plan (forward_mixed_plan): the frame buffer that holds its transform -- L = N / 2 points, or
+// N for an odd size -- and as many frames per workgroup as the LDS takes (128 KB at 1024 points: eight float32 frames, four float64)
+template <typename S, typename Tio>
+void launch_mixed16(const StftJob &job, const GenericArgs &a, const StftTables &t, const MelTail *mel = nullptr) {
+  constexpr int W = sizeof(S) == 8 ? 2 : 1;
+  MixedPlan<S> pl{};
+  pl.npass = t.mixed_npass;
+  for (int i = 0; i < t.mixed_npass; ++i) pl.radices |= (unsigned long long)t.mixed_radix[i] << (4 * i);
+  if constexpr (W == 2) {
+    pl.tw_l = t.mixed_tw_f64;
+    pl.tw_n = t.twiddle_f64;
   } else {
-    // (the helper waves' partial tiles live in the frames' second buffers: no LDS beyond lds)
-    if (mel) return launch(stft_mixed_power16_kernel<LOG2LP, float, true>, *mel);
-    return launch(stft_mixed_power16_kernel<LOG2LP, float, false>, MelTail{});
+    pl.tw_l = t.mixed_tw;
+    pl.tw_n = t.twiddle_f32;
   }
-}
-
-// the float64 interior: Tio = float (float32 audio, float32 / complex64 out) or double (float64 audio, float64 / complex128 out)
-template <int LOG2LP, int FT, typename Tio, bool FULL = false>
-bool launch_mixed_power16_wide(const StftJob &job, GenericArgs a, const StftTables &t, const MixedPlan<double> &pl) {
-  constexpr int LP = 1 << LOG2LP;
-  a.window = t.window_f64;
-  const int64_t blocks = a.lead * ((a.count + FT - 1) / FT);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = (size_t)FT * 2 * LP * sizeof(double2) + (size_t)2 * LP * sizeof(double2);   // frames + the two twiddle tables
-  auto launch = [&](auto kernel) {
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(64 * FT), lds, job.stream, a, pl, MelTail{});
-    SMX_HIP_CHECK(hipGetLastError());
-  };
-  if (job.mode == OUT_COMPLEX) launch(stft_mixed_power16_kernel<LOG2LP, Tio, false, FT, true, double, Tio, FULL>);
-  else launch(stft_mixed_power16_kernel<LOG2LP, Tio, false, FT, false, double, Tio, FULL>);
-  return true;
-}
-
-template <typename Tio>
-bool launch_mixed16_wide_any(const StftJob &job, const GenericArgs &a, const StftTables &t) {
-  if (t.mixed_npass <= 0 || !t.mixed_tw_f64 || !t.window_f64 || !t.twiddle_f64 || !(t.blu2_window || t.mixed_full)) return false;   // (the forward plan's sizes)
-  static const bool off = env_flag("SMX_MIXED_OFF") == 1;
-  if (off) return false;
-  MixedPlan<double> pl{};
-  pl.npass = t.mixed_npass;
-  for (int i = 0; i < t.mixed_npass; ++i) pl.radices |= (unsigned long long)t.mixed_radix[i] << (4 * i);
-  pl.tw_l = t.mixed_tw_f64;
-  pl.tw_n = (const double2 *)t.twiddle_f64;
   if (t.mixed_full) {   // odd N: a transform of N points
     const int64_t n = a.fft;
-    if (n <= 128) return launch_mixed_power16_wide<7, 16, Tio, true>(job, a, t, pl);
-    if (n <= 256) return launch_mixed_power16_wide<8, 16, Tio, true>(job, a, t, pl);
-    if (n <= 512) return launch_mixed_power16_wide<9, 8, Tio, true>(job, a, t, pl);
-    if (n <= 1024) return launch_mixed_power16_wide<10, 4, Tio, true>(job, a, t, pl);
-    return false;
+    if (n <= 128) launch_mixed_power16<7, 16, true, S, Tio>(job, a, t, pl, mel);
+    else if (n <= 256) launch_mixed_power16<8, 16, true, S, Tio>(job, a, t, pl, mel);
+    else if (n <= 512) launch_mixed_power16<9, 16 / W, true, S, Tio>(job, a, t, pl, mel);
+    else launch_mixed_power16<10, 8 / W, true, S, Tio>(job, a, t, pl, mel);
+    return;
   }
   const int64_t l = a.fft / 2;
-  if (l <= 128) return launch_mixed_power16_wide<7, 16, Tio>(job, a, t, pl);
-  if (l <= 256) return launch_mixed_power16_wide<8, 16, Tio>(job, a, t, pl);
-  if (l <= 512) return launch_mixed_power16_wide<9, 8, Tio>(job, a, t, pl);
-  if (l <= 1024) return launch_mixed_power16_wide<10, 4, Tio>(job, a, t, pl);
-  return false;
+  if (l <= 128) launch_mixed_power16<7, 16, false, S, Tio>(job, a, t, pl, mel);
+  else if (l <= 256) launch_mixed_power16<8, 16, false, S, Tio>(job, a, t, pl, mel);
+  else if (l <= 512) launch_mixed_power16<9, 16 / W, false, S, Tio>(job, a, t, pl, mel);
+  else launch_mixed_power16<10, 8 / W, false, S, Tio>(job, a, t, pl, mel);
 }
 
-// true when the size has a mixed-radix plan (StftTables::mixed_npass > 0) and the kernel took the launch
-bool launch_mixed16_any(const StftJob &job, const GenericArgs &a, const StftTables &t, const MelTail *mel) {
-  if (t.mixed_npass <= 0 || !t.mixed_tw || !(t.blu2_window || (t.mixed_full && t.window_f32)) || !t.twiddle_f32) return false;
-  static const bool off = env_flag("SMX_MIXED_OFF") == 1;   // tests / A/B timing: chirp-z instead
-  if (off) return false;
-  MixedPlan<float> pl{};
-  pl.npass = t.mixed_npass;
-  for (int i = 0; i < t.mixed_npass; ++i) pl.radices |= (unsigned long long)t.mixed_radix[i] << (4 * i);
-  pl.tw_l = t.mixed_tw;
-  pl.tw_n = (const float2 *)t.twiddle_f32;
-  if (t.mixed_full) {   // odd N: a transform of N points
-    const int64_t n = a.fft;
-    if (n <= 128) return launch_mixed_power16<7, 16, true>(job, a, t, pl, mel);
-    if (n <= 256) return launch_mixed_power16<8, 16, true>(job, a, t, pl, mel);
-    if (n <= 512) return launch_mixed_power16<9, 16, true>(job, a, t, pl, mel);
-    if (n <= 1024) return launch_mixed_power16<10, 8, true>(job, a, t, pl, mel);
-    return false;
-  }
-  const int64_t l = a.fft / 2;
-  if (l <= 128) return launch_mixed_power16<7>(job, a, t, pl, mel);
-  if (l <= 256) return launch_mixed_power16<8>(job, a, t, pl, mel);
-  if (l <= 512) return launch_mixed_power16<9>(job, a, t, pl, mel);
-  if (l <= 1024) return launch_mixed_power16<10, 8>(job, a, t, pl, mel);   // 128 KB of LDS: eight frames per workgroup, power only
-  return false;
-}
-
-// even non-power-of-two sizes up to 1024 (chirp-z length M <= 1024): power / mel through the 16-frame kernel
-bool launch_bluestein16_any(const StftJob &job, const GenericArgs &a, const StftTables &t, const MelTail *mel) {
+// even sizes up to 1024 without such a plan (chirp-z length M <= 1024): power / mel through the 16-frame chirp-z kernel
+void launch_bluestein16(const StftJob &job, const GenericArgs &a, const StftTables &t, const MelTail *mel) {
   switch (t.blu2_log2m) {
     case 8: return launch_bluestein_power16<8>(job, a, t, mel);
     case 9: return launch_bluestein_power16<9>(job, a, t, mel);
-    case 10: return launch_bluestein_power16<10>(job, a, t, mel);
-    default: return false;
+    default: return launch_bluestein_power16<10>(job, a, t, mel);
   }
 }
 
-template <int LOG2M>
-bool launch_bluestein_real(const StftJob &job, GenericArgs a, const StftTables &t) {
+// the staged chirp-z kernels: half length (even sizes, M = 2^blu2_log2m) or full length (odd sizes, M = 2^blu_log2m)
+template <int LOG2M, bool HALF>
+void launch_bluestein_staged(const StftJob &job, GenericArgs a, const StftTables &t) {
   constexpr int M = 1 << LOG2M, T = M / 16, G = T < 256 ? 256 / T : 1, THREADS = T < 256 ? 256 : T;
-  const size_t elem_out = (job.mode == OUT_COMPLEX ? 2 : 1) * sizeof(float);
-  const size_t work = (size_t)G * M * sizeof(float2);
-  auto stage_bytes = [&](int ft) { return (size_t)a.bins * (size_t)(ft + 1) * elem_out + 16; };
-  int ft = 16;
-  while (ft > G && work + stage_bytes(ft) > kLdsLimit) ft >>= 1;
-  a.direct = work + stage_bytes(ft) > kLdsLimit ? 1 : 0;
-  if (a.direct) ft = G;
-  if (work > kLdsLimit) return false;
-  a.ft = ft;
-  a.window = t.blu2_window;
-  const Blu2Args b{t.blu2_chirp, t.blu2_filter, t.blu2_tw, (const float2 *)t.twiddle_f32};
-  const int64_t blocks = a.lead * ((a.count + ft - 1) / ft);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = a.direct ? work : work + stage_bytes(ft);
-  auto kernel = stft_bluestein_real_kernel<LOG2M, float>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, b);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
+  static_assert((size_t)G * M * sizeof(float2) <= kLdsLimit, "the work buffers fit the LDS");
+  if constexpr (HALF) {
+    a.window = t.blu2_window;
+    launch_staged(stft_bluestein_real_kernel<LOG2M, float>, job, a, G, THREADS, (size_t)G * M * sizeof(float2),
+                  Blu2Args{t.blu2_chirp, t.blu2_filter, t.blu2_tw, (const float2 *)t.twiddle_f32});
+  } else {
+    launch_staged(stft_bluestein_kernel<LOG2M, float>, job, a, G, THREADS, (size_t)G * M * sizeof(float2),
+                  BluArgs{t.blu_chirp, t.blu_post, t.blu_filter, t.blu_tw});
+  }
 }
 
-template <int LOG2M>
-bool launch_bluestein(const StftJob &job, GenericArgs a, const BluArgs &b) {
-  constexpr int M = 1 << LOG2M, T = M / 16, G = T < 256 ? 256 / T : 1, THREADS = T < 256 ? 256 : T;
-  const size_t elem_out = (job.mode == OUT_COMPLEX ? 2 : 1) * sizeof(float);
-  const size_t work = (size_t)G * M * sizeof(float2);
-  auto stage_bytes = [&](int ft) { return (size_t)a.bins * (size_t)(ft + 1) * elem_out + 16; };
-  int ft = 16;
-  while (ft > G && work + stage_bytes(ft) > kLdsLimit) ft >>= 1;
-  a.direct = work + stage_bytes(ft) > kLdsLimit ? 1 : 0;
-  if (a.direct) ft = G;
-  if (work > kLdsLimit) return false;
-  a.ft = ft;
-  const int64_t blocks = a.lead * ((a.count + ft - 1) / ft);
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
-  const size_t lds = a.direct ? work : work + stage_bytes(ft);
-  auto kernel = stft_bluestein_kernel<LOG2M, float>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, job.stream, a, b);
-  SMX_HIP_CHECK(hipGetLastError());
-  return true;
+template <bool HALF>
+void launch_bluestein_any(const StftJob &job, const GenericArgs &a, const StftTables &t) {
+  switch (HALF ? t.blu2_log2m : t.blu_log2m) {
+    case 8: return launch_bluestein_staged<8, HALF>(job, a, t);
+    case 9: return launch_bluestein_staged<9, HALF>(job, a, t);
+    case 10: return launch_bluestein_staged<10, HALF>(job, a, t);
+    case 11: return launch_bluestein_staged<11, HALF>(job, a, t);
+    case 12: return launch_bluestein_staged<12, HALF>(job, a, t);
+    case 13: return launch_bluestein_staged<13, HALF>(job, a, t);
+    default:
+      if constexpr (!HALF) return launch_bluestein_staged<14, false>(job, a, t);
+  }
 }
 
 template <typename Tin, typename Tacc, typename Tout>
@@ -1668,15 +1375,15 @@ void launch_typed(const StftJob &job, GenericArgs a) {
     a.log2n = 0;
     while ((int64_t(1) << a.log2n) < N) ++a.log2n;
   }
-  const size_t lds = work + stage_bytes(ft);
-  const int64_t tiles = (a.count + ft - 1) / ft;
-  const int64_t blocks = a.lead * tiles;
-  if (blocks > 2147483647LL) throw Failure("stft: too many frame tiles for one launch");
   auto kernel = use_pow2 ? stft_generic_kernel<Tin, Tacc, Tout, true> : stft_generic_kernel<Tin, Tacc, Tout, false>;
-  SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(256), lds, job.stream, a);
-  SMX_HIP_CHECK(hipGetLastError());
+  launch_tiles("stft", kernel, a.lead * ((a.count + ft - 1) / ft), 256, work + stage_bytes(ft), job.stream, a);
+}
+
+// the sizes whose forward transform has a mixed-radix plan: N / 2 (even N, not a power of two) or N (odd N) = 2^a 3^b 5^c 7^d <= 1024.
+// (The small powers of two carry a plan for the inverse only: they have neither the halved window nor mixed_full.)
+bool forward_mixed_plan(const StftTables &t) {
+  static const bool off = env_flag("SMX_MIXED_OFF") == 1;   // tests / A/B timing: chirp-z instead
+  return t.mixed_npass > 0 && (t.blu2_window || t.mixed_full) && !off;
 }
 
 }  // namespace
@@ -1694,21 +1401,7 @@ bool launch_mel_spectrogram_16(const MelSpecJob &job) {
   if (diag_flag("SMX_MEL16_OFF") == 1) return false;
   if (sj.count <= 0 || sj.lead <= 0) return true;
   const smx_mel_config::Tables &mtab = job.mel->tables();
-  GenericArgs a{};
-  a.x = sj.x;
-  a.n = sj.n;
-  a.x_stride = sj.x_stride;
-  a.lead = sj.lead;
-  a.fft = c.fft_size;
-  a.hop = c.hop;
-  a.left = sj.left;
-  a.pad = sj.pad;
-  a.pad_value = sj.pad_value;
-  a.p0 = sj.p0;
-  a.count = sj.count;
-  a.mode = (int)sj.mode;
-  a.power = sj.power;
-  a.bins = c.bins();
+  GenericArgs a(sj, t);
   MelTail mt{};
   mt.w = mtab.w_tile;
   mt.band_lo = mtab.tile_lo;
@@ -1720,127 +1413,67 @@ bool launch_mel_spectrogram_16(const MelSpecJob &job) {
   mt.k_pad = (int)mtab.k_pad;
   mt.out = reinterpret_cast<float *>(job.out);
   if (chirp_16) {
-    // Sizes with a mixed-radix plan take the composition power kernel + Mel.apply at EVERY batch size.  The fused launch is
-    // ahead only below a few tiles per CU (one launch instead of two; above, fft 400 / hop 160, 80 mels, 256 x 30 s:
-    // 1.03 + 0.22 ms against 1.50), and its MFMA tail sums in another order than Mel.apply -- a switch by batch size made a
-    // clip's values depend on what it was batched with (the reference's slice law, mel_props.ml:136-155).
-    // SMX_MEL16_FUSED=1 selects the fused form, again for every batch.
+    // Sizes with a mixed-radix plan take the composition power kernel + Mel.apply at EVERY batch size, SMX_MIXED_OFF or not.  A
+    // fused launch is ahead only below a few tiles per CU, and its MFMA tail sums in another order than Mel.apply -- a switch by
+    // batch size would make a clip's values depend on what it was batched with (the reference's slice law, mel_props.ml:136-155).
+    // SMX_MEL16_FUSED=1 (diagnostic builds) selects the fused form, again for every batch.
     static const bool force = diag_flag("SMX_MEL16_FUSED") == 1;
     if (t.mixed_npass > 0 && !force) return false;
-    return launch_mixed16_any(sj, a, t, &mt) || launch_bluestein16_any(sj, a, t, &mt);
+    if (forward_mixed_plan(t)) launch_mixed16<float, float>(sj, a, t, &mt);
+    else launch_bluestein16(sj, a, t, &mt);
+  } else if (c.fft_size == 512) {
+    launch_stockham16<9, 16>(sj, a, t, &mt);
+  } else {
+    launch_stockham16<10, 16>(sj, a, t, &mt);
   }
-  return c.fft_size == 512 ? launch_stockham_power16<9>(sj, a, t, &mt) : launch_stockham_power16<10>(sj, a, t, &mt);
+  return true;
 }
 
+// The float64 interior (in the order of its route table): Tio = float for float32 audio, double for float64
+template <typename Tio>
+static void launch_stft_wide(const StftJob &job, const GenericArgs &a, const StftTables &t) {
+  switch (job.cfg->fft_size) {
+    case 512: return launch_stockham16<9, 16, double, Tio>(job, a, t);
+    case 1024: return launch_stockham16<10, 16, double, Tio>(job, a, t);
+    case 2048:
+      if constexpr (sizeof(Tio) == 4) {
+        if (wide64::serves(job, a)) return wide64::launch(job, a, t);
+      }
+      return launch_stockham16<11, 8, double, Tio>(job, a, t);
+    case 4096: return launch_stockham16<12, 4, double, Tio>(job, a, t);
+    default: break;
+  }
+  if (forward_mixed_plan(t)) return launch_mixed16<double, Tio>(job, a, t);
+  launch_typed<Tio, double, Tio>(job, a);
+}
+
+// One decision per request, in the order of DESIGN.md 4.3's route table: every condition below is a property of the request (size,
+// dtypes, face, the tables its size has), none the outcome of a launch.
 void launch_stft_generic(const StftJob &job) {
   if (job.count <= 0 || job.lead <= 0) return;
-  const smx_stft_config &c = *job.cfg;
-  const StftTables &t = c.tables();
-  GenericArgs a{};
-  a.x = job.x;
-  a.n = job.n;
-  a.x_stride = job.x_stride;
-  a.lead = job.lead;
-  a.fft = c.fft_size;
-  a.hop = c.hop;
-  a.left = job.left;
-  a.pad = job.pad;
-  a.pad_value = job.pad_value;
-  a.p0 = job.p0;
-  a.count = job.count;
-  a.mode = (int)job.mode;
-  a.power = job.power;
-  a.out = job.out;
-  a.out_stride = job.out_stride;
-  a.out_offset = job.out_offset;
-  a.bins = c.bins();
-  const bool f64_interior = job.in_bytes == 8 || job.interior == SMX_INTERIOR_F64;
-  a.window = f64_interior ? (const void *)t.window_f64 : (const void *)t.window_f32;
-  a.twiddle = f64_interior ? (const void *)t.twiddle_f64 : (const void *)t.twiddle_f32;
-  if (job.in_bytes == 4 && !f64_interior && !fast_path_disabled()) {
-    bool done = false;
-    // the half-size real form wins up to 2048 (fft 1024: 343 vs 315 Mframes/s, 512: 735 vs 687); from 4096 on both
-    // forms sit at one 256-thread workgroup per CU (the stage fills the LDS) and the full-size one measured faster
-    const bool full_complex = diag_flag("SMX_STOCKHAM_COMPLEX") == 1;   // diagnostic: force the full-size complex form
-    const bool real_form = !full_complex && c.fft_size <= 2048;
-    const bool staged = diag_flag("SMX_STOCKHAM_STAGED") == 1;   // diagnostic: the staged kernel for fft 512 / 1024 power too
-    const bool power16 = real_form && job.mode != OUT_COMPLEX && !staged;
-    const bool complex16 = real_form && job.mode == OUT_COMPLEX && !staged;
-    if (complex16 && c.fft_size == 512) done = launch_stockham_complex16<9>(job, a, t);
-    if (complex16 && c.fft_size == 1024) done = launch_stockham_complex16<10>(job, a, t);
-    if (complex16 && c.fft_size == 2048) done = launch_stockham_complex16<11>(job, a, t);   // where the fused kernels do not apply
-    if (job.mode == OUT_COMPLEX && !staged && !full_complex && c.fft_size == 4096) done = launch_stockham_complex16<12, 8>(job, a, t);   // eight frames per workgroup (128 KB)
-    if (job.mode == OUT_COMPLEX && !staged && !full_complex && c.fft_size == 8192) done = launch_stockham_complex16<13, 4>(job, a, t);   // four
-    if (power16 && c.fft_size == 512) done = launch_stockham_power16<9>(job, a, t);
-    if (power16 && c.fft_size == 1024) done = launch_stockham_power16<10>(job, a, t);
-    if (power16 && c.fft_size == 2048) done = launch_stockham_power16<11>(job, a, t);      // where the fused kernels do not apply
-    if (job.mode != OUT_COMPLEX && !staged && c.fft_size == 4096) done = launch_stockham_power16<12, 8>(job, a, t);
-    if (job.mode != OUT_COMPLEX && !staged && c.fft_size == 8192) done = launch_stockham_power16<13, 4>(job, a, t);
-    if (!done) switch (c.fft_size) {
-      case 256: done = launch_stockham<8>(job, a); break;
-      case 512: done = real_form ? launch_stockham_real<9, float, float, float>(job, a, t) : launch_stockham<9>(job, a); break;
-      case 1024: done = real_form ? launch_stockham_real<10, float, float, float>(job, a, t) : launch_stockham<10>(job, a); break;
-      case 2048: done = real_form ? launch_stockham_real<11, float, float, float>(job, a, t) : launch_stockham<11>(job, a); break;
-      case 4096: done = real_form ? launch_stockham_real<12, float, float, float>(job, a, t) : launch_stockham<12>(job, a); break;
-      case 8192: done = real_form ? launch_stockham_real<13, float, float, float>(job, a, t) : launch_stockham<13>(job, a); break;
-      case 16384: done = real_form ? launch_stockham_real<14, float, float, float>(job, a, t) : launch_stockham<14>(job, a); break;
-      default: break;
-    }
-    const bool blu_full = diag_flag("SMX_BLUESTEIN_FULL") == 1;   // diagnostic: the full-length chirp-z for even sizes too
-    if (!done && !blu_full && !staged)   // N / 2 = 2^a 3^b 5^c <= 1024: direct mixed-radix transform (power or complex)
-      done = launch_mixed16_any(job, a, t, nullptr);
-    if (!done && t.blu2_log2m >= 8 && t.blu2_log2m <= 10 && job.mode != OUT_COMPLEX && !blu_full && !staged)
-      done = launch_bluestein16_any(job, a, t, nullptr);
-    if (!done && t.blu2_log2m >= 8 && !blu_full) {   // even, not a power of two: half-length chirp-z
-      switch (t.blu2_log2m) {
-        case 8: done = launch_bluestein_real<8>(job, a, t); break;
-        case 9: done = launch_bluestein_real<9>(job, a, t); break;
-        case 10: done = launch_bluestein_real<10>(job, a, t); break;
-        case 11: done = launch_bluestein_real<11>(job, a, t); break;
-        case 12: done = launch_bluestein_real<12>(job, a, t); break;
-        case 13: done = launch_bluestein_real<13>(job, a, t); break;
-        default: break;
-      }
-    }
-    if (!done && t.blu_log2m >= 8) {   // not a power of two: chirp-z
-      const BluArgs b{t.blu_chirp, t.blu_post, t.blu_filter, t.blu_tw};
-      switch (t.blu_log2m) {
-        case 8: done = launch_bluestein<8>(job, a, b); break;
-        case 9: done = launch_bluestein<9>(job, a, b); break;
-        case 10: done = launch_bluestein<10>(job, a, b); break;
-        case 11: done = launch_bluestein<11>(job, a, b); break;
-        case 12: done = launch_bluestein<12>(job, a, b); break;
-        case 13: done = launch_bluestein<13>(job, a, b); break;
-        case 14: done = launch_bluestein<14>(job, a, b); break;
-        default: break;
-      }
-    }
-    if (done) return;
+  const StftTables &t = job.cfg->tables();
+  const GenericArgs a(job, t);
+  const bool wide = job.in_bytes == 8 || job.interior == SMX_INTERIOR_F64;
+  if (fast_path_disabled()) {   // SMX_DISABLE_FAST: the radix-2 / direct kernel for everything
+    if (!wide) return launch_typed<float, float, float>(job, a);
+    return job.in_bytes == 8 ? launch_typed<double, double, double>(job, a) : launch_typed<float, double, float>(job, a);
   }
-  if (f64_interior && job.mode == OUT_COMPLEX && !fast_path_disabled()) {   // stage-free complex kernel on doubles
-    if (diag_flag("SMX_STOCKHAM_STAGED") != 1 && (job.in_bytes == 8 ? launch_stockham_complex16_wide_any<double>(job, a, t, c.fft_size)
-                                                        : launch_stockham_complex16_wide_any<float>(job, a, t, c.fft_size)))
-      return;
+  if (wide) return job.in_bytes == 8 ? launch_stft_wide<double>(job, a, t) : launch_stft_wide<float>(job, a, t);
+  switch (job.cfg->fft_size) {   // powers of two: the half-size real form, as many frames per workgroup as 128 KB of LDS take
+    case 256: return launch_stockham<8>(job, a);
+    case 512: return launch_stockham16<9, 16>(job, a, t);
+    case 1024: return launch_stockham16<10, 16>(job, a, t);
+    case 2048: return launch_stockham16<11, 16>(job, a, t);   // (what the fused kernels of stft_fast.hip do not take)
+    case 4096: return launch_stockham16<12, 8>(job, a, t);
+    case 8192: return launch_stockham16<13, 4>(job, a, t);
+    case 16384: return launch_stockham<14>(job, a);
+    default: break;
   }
-  if (f64_interior && job.mode != OUT_COMPLEX && !fast_path_disabled()) {   // stage-free power kernel on doubles
-    if (diag_flag("SMX_STOCKHAM_STAGED") != 1 && (job.in_bytes == 8 ? launch_stockham_power16_wide_any<double>(job, a, t, c.fft_size)
-                                                        : launch_stockham_power16_wide_any<float>(job, a, t, c.fft_size)))
-      return;
-  }
-  if (f64_interior && !fast_path_disabled()) {   // even sizes with N / 2 = 2^a 3^b 5^c: the mixed-radix kernel on doubles
-    if (job.in_bytes == 8 ? launch_mixed16_wide_any<double>(job, a, t) : launch_mixed16_wide_any<float>(job, a, t)) return;
-  }
-  if (f64_interior && !fast_path_disabled()) {   // float64 interior on the Stockham passes (fft 512 .. 4096)
-    if (job.in_bytes == 8 ? launch_stockham_wide<double, double>(job, a, t, c.fft_size)
-                          : launch_stockham_wide<float, float>(job, a, t, c.fft_size))
-      return;
-  }
-  if (job.in_bytes == 8)
-    launch_typed<double, double, double>(job, a);
-  else if (f64_interior)
-    launch_typed<float, double, float>(job, a);
-  else
-    launch_typed<float, float, float>(job, a);
+  if (forward_mixed_plan(t)) return launch_mixed16<float, float>(job, a, t);
+  if (t.blu2_log2m >= 8 && t.blu2_log2m <= 10 && job.mode != OUT_COMPLEX) return launch_bluestein16(job, a, t, nullptr);
+  if (t.blu2_log2m >= 8 && t.blu2_log2m <= 13) return launch_bluestein_any<true>(job, a, t);   // even sizes up to 8192
+  if (t.blu_log2m >= 8) return launch_bluestein_any<false>(job, a, t);                          // odd sizes up to 8191
+  launch_typed<float, float, float>(job, a);
 }
 
 }  // namespace smx

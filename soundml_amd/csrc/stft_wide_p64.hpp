@@ -471,20 +471,19 @@ __global__ void __launch_bounds__(512) stft2048_power_wide_kernel(Args A) {
   }
 }
 
-// the launch: true = taken (fft 2048, float32 audio, power output, row offsets within 32 bits)
-inline bool launch(const StftJob &job, const GenericArgs &g, const StftTables &t) {
-  if (job.cfg->fft_size != kN || job.in_bytes != 4 || job.mode == OUT_COMPLEX) return false;
-  if (!t.window_f64 || !t.fast_w_m_f64 || !t.twiddle_f64) return false;
-  if (g.bins * g.out_stride * 4 >= (int64_t(1) << 32)) return false;
-  if (g.count <= 0 || g.lead <= 0) return true;
-  if (env_flag("SMX_WIDE_PIPELINE") == 0) return false;   // "0": the one-tile-per-workgroup kernel (A/B timing, bit-identical)
+// what the kernel takes of the fft-2048 / float32-audio / power requests: row offsets within 32 bits, tile counts within 31
+inline bool serves(const StftJob &job, const GenericArgs &g) {
+  if (job.mode == OUT_COMPLEX || g.bins * g.out_stride * 4 >= (int64_t(1) << 32) || (g.count + kFT - 1) / kFT > 0x7fffffff) return false;
+  return env_flag("SMX_WIDE_PIPELINE") != 0;   // "0": the one-tile-per-workgroup kernel (A/B timing, bit-identical)
+}
+
+inline void launch(const StftJob &job, const GenericArgs &g, const StftTables &t) {
   Args A{};
   A.g = g;
   A.window = reinterpret_cast<const double *>(t.window_f64);
   A.tw_m = reinterpret_cast<const V2 *>(t.fast_w_m_f64);
   A.tw_n = reinterpret_cast<const V2 *>(t.twiddle_f64);
   const int64_t tiles = (g.count + kFT - 1) / kFT;
-  if (tiles > 0x7fffffff) return false;
   A.tiles_per_clip = (int)tiles;
   A.total_tiles = g.lead * tiles;
   const int cu_count = device_cu_count();   // (per device, thread-safe: tables.cpp)
@@ -494,6 +493,5 @@ inline bool launch(const StftJob &job, const GenericArgs &g, const StftTables &t
   SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
   SMX_LAUNCH(kernel, dim3((unsigned)A.blocks), dim3(512), kLds, job.stream, A);
   SMX_HIP_CHECK(hipGetLastError());
-  return true;
 }
 }  // namespace wide64

@@ -20,6 +20,59 @@ T *upload(const std::vector<T> &host) {
 
 bool is_pow2(int64_t n) { return n >= 1 && (n & (n - 1)) == 0; }
 
+// exp(-2 pi i j / period), j < count, computed in float64
+template <typename V>
+std::vector<V> unit_roots(int64_t count, int64_t period) {
+  std::vector<V> w((size_t)count);
+  for (int64_t j = 0; j < count; ++j) {
+    const double a = -2.0 * M_PI * (double)j / (double)period;
+    w[(size_t)j].x = (decltype(w[0].x))std::cos(a);
+    w[(size_t)j].y = (decltype(w[0].x))std::sin(a);
+  }
+  return w;
+}
+
+// pi i^2 / len with i^2 reduced modulo 2 len (the chirp has that period)
+double chirp_angle(int64_t i, int64_t len) { return M_PI * (double)((i * i) % (2 * len)) / (double)len; }
+
+// chirp-z over `len` points as a circular convolution of m = 2^log2m >= 2 len - 1: the filter b[j] = exp(+i pi j^2 / len) for
+// |j| < len, wrapped into m points; its spectrum by an in-place float64 radix-2 DIF transform, unscrambled, with the inverse
+// transform's 1/m folded in
+std::vector<float2> chirp_filter(int64_t len, int log2m) {
+  const int64_t m = int64_t(1) << log2m;
+  std::vector<double> re((size_t)m, 0.0), im((size_t)m, 0.0);
+  for (int64_t j = 0; j < len; ++j) {
+    const double a = chirp_angle(j, len);
+    re[(size_t)j] = std::cos(a);
+    im[(size_t)j] = std::sin(a);
+    if (j > 0) {
+      re[(size_t)(m - j)] = re[(size_t)j];
+      im[(size_t)(m - j)] = im[(size_t)j];
+    }
+  }
+  for (int64_t half = m >> 1; half >= 1; half >>= 1) {
+    const int64_t tstep = (m >> 1) / half;
+    for (int64_t b = 0; b < (m >> 1); ++b) {
+      const int64_t j = b & (half - 1);
+      const int64_t i0 = ((b - j) << 1) + j, i1 = i0 + half;
+      const double ang = -2.0 * M_PI * (double)(j * tstep) / (double)m;
+      const double wr = std::cos(ang), wi = std::sin(ang);
+      const double dr = re[(size_t)i0] - re[(size_t)i1], di = im[(size_t)i0] - im[(size_t)i1];
+      re[(size_t)i0] += re[(size_t)i1];
+      im[(size_t)i0] += im[(size_t)i1];
+      re[(size_t)i1] = dr * wr - di * wi;
+      im[(size_t)i1] = dr * wi + di * wr;
+    }
+  }
+  std::vector<float2> filt((size_t)m);
+  for (int64_t i = 0; i < m; ++i) {
+    unsigned k = 0;
+    for (int bit = 0; bit < log2m; ++bit) k |= ((unsigned)(i >> bit) & 1u) << (log2m - 1 - bit);   // position i holds B[brev(i)]
+    filt[k] = make_float2((float)(re[(size_t)i] / (double)m), (float)(im[(size_t)i] / (double)m));
+  }
+  return filt;
+}
+
 }  // namespace
 
 // Scratch arrays (Griffin-Lim's spectra, the scratch spectrogram of the unfused compositions, small tables) come
@@ -125,154 +178,58 @@ const smx::StftTables &smx_stft_config::tables() const {
   t.window_f64 = smx::upload(analysis_window);
   t.window_f32 = smx::upload(w32);
 
-  // generic kernels: N twiddles exp(-2 pi i j / N) (the radix-2 passes read j < N/2,
-  // the direct DFT all N)
-  const int64_t tw = n;
-  std::vector<double2> t64((size_t)tw);
-  std::vector<float2> t32((size_t)tw);
-  for (int64_t j = 0; j < tw; ++j) {
-    const double a = -2.0 * M_PI * (double)j / (double)n;
-    t64[(size_t)j] = make_double2(std::cos(a), std::sin(a));
-    t32[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-  }
-  t.twiddle_f64 = smx::upload(t64);
-  t.twiddle_f32 = smx::upload(t32);
-  t.twiddle_len = tw;
+  // generic kernels: N twiddles exp(-2 pi i j / N) (the radix-2 passes read j < N/2, the direct DFT all N)
+  t.twiddle_f64 = smx::upload(smx::unit_roots<double2>(n, n));
+  t.twiddle_f32 = smx::upload(smx::unit_roots<float2>(n, n));
 
-  // chirp-z tables for sizes that are not powers of two (M = 256 .. 16384: N <= 8192)
-  if (!smx::is_pow2(n) && n >= 2) {
+  // odd sizes up to 8191: chirp-z over the frame's N points (M = 256 .. 16384)
+  if (n % 2 == 1 && n >= 3) {
     int log2m = 8;
     while ((int64_t(1) << log2m) < 2 * n - 1) ++log2m;
     if (log2m <= 14) {
-      const int64_t m = int64_t(1) << log2m;
-      auto chirp_angle = [&](int64_t i) {   // pi i^2 / N with i^2 reduced modulo 2 N (the chirp has that period)
-        const int64_t r = (i * i) % (2 * n);
-        return M_PI * (double)r / (double)n;
-      };
-      std::vector<float2> chirp((size_t)n), post((size_t)n), tw((size_t)(m / 2));
+      std::vector<float2> chirp((size_t)n), post((size_t)n);
       for (int64_t i = 0; i < n; ++i) {
-        const double a = chirp_angle(i), w = analysis_window[(size_t)i];
+        const double a = smx::chirp_angle(i, n), w = analysis_window[(size_t)i];
         chirp[(size_t)i] = make_float2((float)(w * std::cos(a)), (float)(-w * std::sin(a)));
         post[(size_t)i] = make_float2((float)std::cos(a), (float)(-std::sin(a)));
       }
-      // filter b[j] = exp(+i pi j^2 / N) for |j| < N, wrapped into M points; its spectrum by an in-place
-      // float64 radix-2 DIF transform, unscrambled, with the inverse transform's 1/M folded in
-      std::vector<double> re((size_t)m, 0.0), im((size_t)m, 0.0);
-      for (int64_t j = 0; j < n; ++j) {
-        const double a = chirp_angle(j);
-        re[(size_t)j] = std::cos(a);
-        im[(size_t)j] = std::sin(a);
-        if (j > 0) {
-          re[(size_t)(m - j)] = std::cos(a);
-          im[(size_t)(m - j)] = std::sin(a);
-        }
-      }
-      for (int64_t half = m >> 1; half >= 1; half >>= 1) {
-        const int64_t tstep = (m >> 1) / half;
-        for (int64_t b = 0; b < (m >> 1); ++b) {
-          const int64_t j = b & (half - 1);
-          const int64_t i0 = ((b - j) << 1) + j, i1 = i0 + half;
-          const double ang = -2.0 * M_PI * (double)(j * tstep) / (double)m;
-          const double wr = std::cos(ang), wi = std::sin(ang);
-          const double dr = re[(size_t)i0] - re[(size_t)i1], di = im[(size_t)i0] - im[(size_t)i1];
-          re[(size_t)i0] += re[(size_t)i1];
-          im[(size_t)i0] += im[(size_t)i1];
-          re[(size_t)i1] = dr * wr - di * wi;
-          im[(size_t)i1] = dr * wi + di * wr;
-        }
-      }
-      std::vector<float2> filt((size_t)m);
-      for (int64_t i = 0; i < m; ++i) {
-        unsigned k = 0;
-        for (int bit = 0; bit < log2m; ++bit) k |= ((unsigned)(i >> bit) & 1u) << (log2m - 1 - bit);   // position i holds B[brev(i)]
-        filt[k] = make_float2((float)(re[(size_t)i] / (double)m), (float)(im[(size_t)i] / (double)m));
-      }
-      for (int64_t j = 0; j < m / 2; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)m;
-        tw[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-      }
       t.blu_chirp = smx::upload(chirp);
       t.blu_post = smx::upload(post);
-      t.blu_filter = smx::upload(filt);
-      t.blu_tw = smx::upload(tw);
+      t.blu_filter = smx::upload(smx::chirp_filter(n, log2m));
+      t.blu_tw = smx::upload(smx::unit_roots<float2>((int64_t(1) << log2m) / 2, int64_t(1) << log2m));
       t.blu_log2m = log2m;
     }
-    // even sizes: the frame as ONE chirp-z transform of length L = N/2 over its (even, odd) sample pairs, then the
-    // real-input post-pass -- a quarter of the convolution work (fft 400: M = 512 instead of 1024)
-    if (n % 2 == 0 && n >= 4) {
-      const int64_t l = n / 2;
-      int log2m2 = 8;
-      while ((int64_t(1) << log2m2) < 2 * l - 1) ++log2m2;
-      if (log2m2 <= 14) {
-        const int64_t m = int64_t(1) << log2m2;
-        auto angle = [&](int64_t i) { return M_PI * (double)((i * i) % (2 * l)) / (double)l; };
-        std::vector<float2> chirp((size_t)l), tw((size_t)(m / 2));
-        std::vector<float> hw((size_t)n);
-        for (int64_t i = 0; i < n; ++i) hw[(size_t)i] = (float)(0.5 * analysis_window[(size_t)i]);
-        for (int64_t i = 0; i < l; ++i) chirp[(size_t)i] = make_float2((float)std::cos(angle(i)), (float)(-std::sin(angle(i))));
-        std::vector<double> re((size_t)m, 0.0), im((size_t)m, 0.0);
-        for (int64_t j = 0; j < l; ++j) {
-          re[(size_t)j] = std::cos(angle(j));
-          im[(size_t)j] = std::sin(angle(j));
-          if (j > 0) {
-            re[(size_t)(m - j)] = re[(size_t)j];
-            im[(size_t)(m - j)] = im[(size_t)j];
-          }
-        }
-        for (int64_t half = m >> 1; half >= 1; half >>= 1) {   // in-place float64 radix-2 DIF, bit-reversed output
-          const int64_t tstep = (m >> 1) / half;
-          for (int64_t b = 0; b < (m >> 1); ++b) {
-            const int64_t j = b & (half - 1);
-            const int64_t i0 = ((b - j) << 1) + j, i1 = i0 + half;
-            const double ang = -2.0 * M_PI * (double)(j * tstep) / (double)m;
-            const double wr = std::cos(ang), wi = std::sin(ang);
-            const double dr = re[(size_t)i0] - re[(size_t)i1], di = im[(size_t)i0] - im[(size_t)i1];
-            re[(size_t)i0] += re[(size_t)i1];
-            im[(size_t)i0] += im[(size_t)i1];
-            re[(size_t)i1] = dr * wr - di * wi;
-            im[(size_t)i1] = dr * wi + di * wr;
-          }
-        }
-        std::vector<float2> filt((size_t)m);
-        for (int64_t i = 0; i < m; ++i) {
-          unsigned k = 0;
-          for (int bit = 0; bit < log2m2; ++bit) k |= ((unsigned)(i >> bit) & 1u) << (log2m2 - 1 - bit);
-          filt[k] = make_float2((float)(re[(size_t)i] / (double)m), (float)(im[(size_t)i] / (double)m));
-        }
-        for (int64_t j = 0; j < m / 2; ++j) {
-          const double a = -2.0 * M_PI * (double)j / (double)m;
-          tw[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        t.blu2_chirp = smx::upload(chirp);
-        t.blu2_filter = smx::upload(filt);
-        t.blu2_tw = smx::upload(tw);
-        t.blu2_window = smx::upload(hw);
-        t.blu2_log2m = log2m2;
-        // L = 2^a 3^b 5^c 7^d <= 1024 (and not a power of two: those have the Stockham kernels): radices 4, 2, 5, 3, 7
-        if (l <= 1024 && (l & (l - 1)) != 0) {
-          int64_t rest = l;
-          int np = 0, radix[10];
-          while (rest % 4 == 0 && np < 10) { radix[np++] = 4; rest /= 4; }
-          while (rest % 2 == 0 && np < 10) { radix[np++] = 2; rest /= 2; }
-          while (rest % 5 == 0 && np < 10) { radix[np++] = 5; rest /= 5; }
-          while (rest % 3 == 0 && np < 10) { radix[np++] = 3; rest /= 3; }
-          while (rest % 7 == 0 && np < 10) { radix[np++] = 7; rest /= 7; }
-          if (rest == 1 && np > 0) {
-            std::vector<float2> twl((size_t)l);
-            for (int64_t j = 0; j < l; ++j) {
-              const double a = -2.0 * M_PI * (double)j / (double)l;
-              twl[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-            }
-            t.mixed_tw = smx::upload(twl);
-            std::vector<double2> twd((size_t)l);
-            for (int64_t j = 0; j < l; ++j) {
-              const double a = -2.0 * M_PI * (double)j / (double)l;
-              twd[(size_t)j] = make_double2(std::cos(a), std::sin(a));
-            }
-            t.mixed_tw_f64 = smx::upload(twd);
-            t.mixed_npass = np;
-            for (int i = 0; i < np; ++i) t.mixed_radix[i] = radix[i];
-          }
+  }
+  // even sizes that are not powers of two: the frame as ONE chirp-z transform of length L = N/2 over its (even, odd) sample pairs,
+  // then the real-input post-pass -- a quarter of the convolution work (fft 400: M = 512 instead of 1024)
+  if (!smx::is_pow2(n) && n % 2 == 0 && n >= 4) {
+    const int64_t l = n / 2;
+    int log2m2 = 8;
+    while ((int64_t(1) << log2m2) < 2 * l - 1) ++log2m2;
+    if (log2m2 <= 14) {
+      std::vector<float2> chirp((size_t)l);
+      std::vector<float> hw((size_t)n);
+      for (int64_t i = 0; i < n; ++i) hw[(size_t)i] = (float)(0.5 * analysis_window[(size_t)i]);
+      for (int64_t i = 0; i < l; ++i) chirp[(size_t)i] = make_float2((float)std::cos(smx::chirp_angle(i, l)), (float)(-std::sin(smx::chirp_angle(i, l))));
+      t.blu2_chirp = smx::upload(chirp);
+      t.blu2_filter = smx::upload(smx::chirp_filter(l, log2m2));
+      t.blu2_tw = smx::upload(smx::unit_roots<float2>((int64_t(1) << log2m2) / 2, int64_t(1) << log2m2));
+      t.blu2_window = smx::upload(hw);
+      t.blu2_log2m = log2m2;
+      // L = 2^a 3^b 5^c 7^d <= 1024 (and not a power of two: those have the Stockham kernels): radices 4, 2, 5, 3, 7
+      if (l <= 1024 && (l & (l - 1)) != 0) {
+        int64_t rest = l;
+        int np = 0, radix[10];
+        while (rest % 4 == 0 && np < 10) { radix[np++] = 4; rest /= 4; }
+        while (rest % 2 == 0 && np < 10) { radix[np++] = 2; rest /= 2; }
+        while (rest % 5 == 0 && np < 10) { radix[np++] = 5; rest /= 5; }
+        while (rest % 3 == 0 && np < 10) { radix[np++] = 3; rest /= 3; }
+        while (rest % 7 == 0 && np < 10) { radix[np++] = 7; rest /= 7; }
+        if (rest == 1 && np > 0) {
+          t.mixed_tw = smx::upload(smx::unit_roots<float2>(l, l));
+          t.mixed_tw_f64 = smx::upload(smx::unit_roots<double2>(l, l));
+          t.mixed_npass = np;
+          for (int i = 0; i < np; ++i) t.mixed_radix[i] = radix[i];
         }
       }
     }
@@ -287,15 +244,8 @@ const smx::StftTables &smx_stft_config::tables() const {
     while (rest % 3 == 0 && np < 10) { radix[np++] = 3; rest /= 3; }
     while (rest % 7 == 0 && np < 10) { radix[np++] = 7; rest /= 7; }
     if (rest == 1 && np > 0) {
-      std::vector<float2> twl((size_t)n);
-      std::vector<double2> twd((size_t)n);
-      for (int64_t j = 0; j < n; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)n;
-        twl[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-        twd[(size_t)j] = make_double2(std::cos(a), std::sin(a));
-      }
-      t.mixed_tw = smx::upload(twl);
-      t.mixed_tw_f64 = smx::upload(twd);
+      t.mixed_tw = smx::upload(smx::unit_roots<float2>(n, n));
+      t.mixed_tw_f64 = smx::upload(smx::unit_roots<double2>(n, n));
       t.mixed_npass = np;
       t.mixed_full = 1;
       for (int i = 0; i < np; ++i) t.mixed_radix[i] = radix[i];
@@ -308,18 +258,8 @@ const smx::StftTables &smx_stft_config::tables() const {
     int np = 0;
     while (rest % 4 == 0 && np < 10) { t.mixed_radix[np++] = 4; rest /= 4; }
     while (rest % 2 == 0 && np < 10) { t.mixed_radix[np++] = 2; rest /= 2; }
-    std::vector<float2> twl((size_t)(n / 2));
-    for (int64_t j = 0; j < n / 2; ++j) {
-      const double a = -2.0 * M_PI * (double)j / (double)(n / 2);
-      twl[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    t.mixed_tw = smx::upload(twl);
-    std::vector<double2> twd((size_t)(n / 2));
-    for (int64_t j = 0; j < n / 2; ++j) {
-      const double a = -2.0 * M_PI * (double)j / (double)(n / 2);
-      twd[(size_t)j] = make_double2(std::cos(a), std::sin(a));
-    }
-    t.mixed_tw_f64 = smx::upload(twd);
+    t.mixed_tw = smx::upload(smx::unit_roots<float2>(n / 2, n / 2));
+    t.mixed_tw_f64 = smx::upload(smx::unit_roots<double2>(n / 2, n / 2));
     t.mixed_npass = np;
   }
 
@@ -328,35 +268,21 @@ const smx::StftTables &smx_stft_config::tables() const {
     const int64_t m = n / 2;
     std::vector<float> hw((size_t)n);
     for (int64_t i = 0; i < n; ++i) hw[(size_t)i] = (float)(0.5 * analysis_window[(size_t)i]);
-    std::vector<float2> wm((size_t)m), wn((size_t)m + 1);
-    for (int64_t j = 0; j < m; ++j) {
-      const double a = -2.0 * M_PI * (double)j / (double)m;
-      wm[(size_t)j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    for (int64_t k = 0; k <= m; ++k) {
-      const double a = -2.0 * M_PI * (double)k / (double)n;
-      wn[(size_t)k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
     // synthesis: the window with the inverse transform's 1/(2M) and the conj(FFT(conj .)) sign folded in
     std::vector<float2> sw((size_t)m);
     for (int64_t j = 0; j < m; ++j)
       sw[(size_t)j] = make_float2((float)(analysis_window[(size_t)(2 * j)] / (double)(2 * m)),
                                   (float)(-analysis_window[(size_t)(2 * j + 1)] / (double)(2 * m)));
     if (n >= 512 && n <= 4096) {
-      std::vector<double2> wm64((size_t)m);
-      for (int64_t j = 0; j < m; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)m;
-        wm64[(size_t)j] = make_double2(std::cos(a), std::sin(a));
-      }
-      t.fast_w_m_f64 = smx::upload(wm64);
+      t.fast_w_m_f64 = smx::upload(smx::unit_roots<double2>(m, m));
       std::vector<double2> sw64((size_t)m);
       for (int64_t j = 0; j < m; ++j)
         sw64[(size_t)j] = make_double2(analysis_window[(size_t)(2 * j)] / (double)(2 * m), -analysis_window[(size_t)(2 * j + 1)] / (double)(2 * m));
       t.fast_synth_window_f64 = smx::upload(sw64);
     }
     t.fast_window = smx::upload(hw);
-    t.fast_w_m = smx::upload(wm);
-    t.fast_w_n = smx::upload(wn);
+    t.fast_w_m = smx::upload(smx::unit_roots<float2>(m, m));
+    t.fast_w_n = smx::upload(smx::unit_roots<float2>(m + 1, n));
     t.fast_synth_window = smx::upload(sw);
   }
   return tables_.emplace(device, t).first->second;

@@ -378,11 +378,95 @@ np.savez(sys.argv[1], **out)
         assert not np.array_equal(res[0][k], res[1][k]), "both runs took the same kernel"
 
 
+# ---- the routes of launch_stft_generic / launch_istft that nothing above reaches, each at its smallest request ----
+
+@pytest.mark.parametrize("fft,face", [(256, "power"), (256, "complex"), (512, "power"), (512, "complex"), (1024, "power"), (1024, "complex"),
+                                      (2048, "power"), (2048, "complex"), (4096, "power")])
+def test_generic_route_beyond_65535_clips(fft, face):
+    """The hand-laid kernels take at most 65535 clips per call; one more and float32 audio at fft 256 .. 2048 (and the power face at
+    4096) runs on stft_generic.hip's Stockham kernels.  65536 one-frame clips (eight distinct ones, repeated): the first eight against
+    the oracle, and every repetition the same bits (a clip's values do not depend on where it sits in the batch)."""
+    import torch
+    x8 = np.random.default_rng(fft).uniform(-1, 1, size=(8, fft)).astype(np.float32)
+    x = torch.from_numpy(x8).cuda().repeat(8192, 1)
+    c, o = Stft.Config.create(fft_size=fft, hop=fft, alignment="left"), O.stft_config(fft, hop=fft, alignment="left")
+    assert Stft.frames(c, fft) == 1
+    if face == "power":
+        got, want = Stft.power_spectrum(c, x), O.power_spectrum(o, x8)
+    else:
+        got, want = torch.view_as_real(Stft.transform(c, x)), O.transform(o, x8)
+        want = np.stack([want.real, want.imag], axis=-1)
+    assert got.is_cuda and tuple(got.shape[:3]) == (65536, fft // 2 + 1, 1)
+    check_fast(got[:8].cpu().numpy(), want, "%d %s" % (fft, face))
+    assert torch.equal(got.reshape(8192, 8, -1), got[:8].reshape(1, 8, -1).expand(8192, -1, -1))
+
+
+@pytest.mark.parametrize("fft", [22, 118, 262, 514, 1028, 131, 257, 521, 1025, 2049, 8194])
+def test_chirp_z_and_direct_dft_sizes(fft):
+    """Sizes without a mixed-radix plan.  Even ones (half length with a prime factor above 7): the half-length chirp-z, M = 256 (fft 22,
+    118), 512, 1024, 2048 -- power through the stage-free kernel up to fft 1024, everything else through the staged one.  Odd ones: the
+    full-length chirp-z, M = 256 .. 4096 (8191 -> 16384 and 31 -> 64 are covered above).  fft 8194: past every chirp-z table, the direct DFT.
+    Spectrum and power against the oracle, a ragged last tile and reflected borders; float32 audio under the float64 interior (the
+    direct DFT on doubles) at the reference's float32 tolerance."""
+    rng = np.random.default_rng(fft)
+    hop = max(1, fft // 4)
+    n = (19 if fft < 8000 else 2) * hop + fft + 3
+    x = rng.uniform(-1, 1, size=(2, n)).astype(np.float32)
+    c, o = Stft.Config.create(fft_size=fft, hop=hop), O.stft_config(fft, hop=hop)
+    z, want = Stft.transform(c, x), O.transform(o, x)
+    assert z.shape == want.shape and z.dtype == np.complex64
+    check_fast(z.real, want.real, "re")
+    check_fast(z.imag, want.imag, "im")
+    wp = O.power_spectrum(o, x)
+    check_fast(Stft.power_spectrum(c, x), wp, "power")
+    S.set_interior("float64")
+    z64, p64 = Stft.transform(c, x), Stft.power_spectrum(c, x)
+    assert z64.dtype == np.complex64 and p64.dtype == np.float32
+    np.testing.assert_allclose(z64, want, rtol=F32_RTOL, atol=F32_ATOL * float(np.max(np.abs(want))))
+    np.testing.assert_allclose(p64, wp, rtol=2 * F32_RTOL, atol=F32_ATOL * float(np.max(np.abs(want))) ** 2)
+
+
+@pytest.mark.parametrize("fft,n_mels,sr", [(118, 10, 8000), (262, 20, 16000), (514, 40, 16000)])
+def test_fused_mel_spectrogram_chirp_z_sizes(fft, n_mels, sr):
+    """Soundml.mel_spectrogram at even sizes up to 1024 without a mixed-radix plan: stft_bluestein_power16_kernel<8 | 9 | 10, MEL>, the
+    chirp-z columns straight into the MFMA tail; against the oracle."""
+    hop = fft // 4
+    x = np.random.default_rng(fft + 7).uniform(-1, 1, size=(2, 37 * hop + 11)).astype(np.float32)
+    c, o = Stft.Config.create(fft_size=fft, hop=hop), O.stft_config(fft, hop=hop)
+    check_fast(S.mel_spectrogram(c, Mel.Config.create(n_mels=n_mels, sample_rate=sr, fft_size=fft), x),
+               O.mel_spectrogram(o, O.mel_config(n_mels, sr, fft), x), "mel %d" % fft)
+
+
+@pytest.mark.parametrize("fft", [9, 225, 441, 945, 1000])
+def test_mixed_radix_remaining_faces(fft):
+    """What test_mixed_radix_* leave out.  Odd sizes (frame buffers of 128, 256, 512, 1024 points): the power face on doubles, float64
+    audio at the reference's float64 tolerance and float32 audio under the float64 interior at its float32 one, where the spectrum is
+    checked too.  fft 1000: the complex face of the 512-point buffer on float32."""
+    rng = np.random.default_rng(fft + 4)
+    hop = max(1, fft // 4)
+    n = 21 * hop + fft + 2
+    x64 = rng.uniform(-1, 1, size=(2, n))
+    x32 = x64.astype(np.float32)
+    c, o = Stft.Config.create(fft_size=fft, hop=hop), O.stft_config(fft, hop=hop)
+    if fft % 2 == 0:
+        z, want = Stft.transform(c, x32), O.transform(o, x32)
+        check_fast(z.real, want.real, "re")
+        check_fast(z.imag, want.imag, "im")
+        return
+    check_close(Stft.power_spectrum(c, x64), O.power_spectrum(o, x64), rtol=4 * F64_RTOL, atol=1e-10, msg="power f64")
+    S.set_interior("float64")
+    z32, w32 = Stft.transform(c, x32), O.transform(o, x32)
+    assert z32.dtype == np.complex64
+    assert np.max(np.abs(z32 - w32)) <= 2e-7 * float(np.max(np.abs(w32)))                      # one rounding of a float64 result
+    p32, wp = Stft.power_spectrum(c, x32), O.power_spectrum(o, x32)
+    assert p32.dtype == np.float32 and np.max(np.abs(p32 - wp)) <= 4e-7 * float(np.max(wp))
+
+
 @pytest.mark.parametrize("fft,hop,alignment,pad", [(512, 128, "centered", "reflect"), (1024, 256, "left", "edge"),
                                                    (2048, 512, "centered", "reflect"), (2048, 500, "right", ("constant", 0.5)),
                                                    (4096, 1024, "centered", "reflect"), (1024, 1500, "centered", "edge")])
 def test_float64_interior_stockham_sizes(fft, hop, alignment, pad):
-    """The float64 interior on the Stockham passes (fft 512 .. 4096, stft_stockham_real_kernel<.., double, ..>):
+    """The float64 interior on the Stockham passes (fft 512 .. 4096, stft_stockham_power16_kernel / stft_stockham_complex16_kernel on doubles):
     float64 audio at the reference's float64 tolerance, float32 audio with `set_interior("float64")` at its float32
     one (stft_goldens.ml:13-17), spectrum and power, borders and ragged tiles, a scaled window; frame ranges
     reassemble the whole bit for bit."""
@@ -669,6 +753,55 @@ def test_invert_vs_oracle(fft, hop, win, alignment, length_mode):
     got32 = Stft.invert(c, z32, length)
     assert got32.dtype == np.float32
     check_fast(got32, O.invert(o, z32, length), "float32")
+
+
+def test_invert_one_tile_per_workgroup_kernel():
+    """SMX_INVERT_PIPELINE=0: Stft.invert at fft 2048 / hop 512 on istft2048_kernel, one tile per workgroup, instead of
+    the persistent pipeline; 2 clips x 40 frames, against the default route at test_invert_goldens' float32-interior tolerance (the
+    switch is read in the library, so each setting runs in a child process)."""
+    code = """
+import sys, numpy as np
+sys.path.insert(0, %r)
+from soundml_amd import Stft
+rng = np.random.default_rng(2048)
+z = (rng.standard_normal((2, 1025, 40)) + 1j * rng.standard_normal((2, 1025, 40))).astype(np.complex64)
+np.save(sys.argv[1], Stft.invert(Stft.Config.create(fft_size=2048, hop=512), z))
+""" % ROOT
+    import subprocess, sys, tempfile
+    res = []
+    for pipeline in ("1", "0"):
+        path = tempfile.mktemp(suffix=".npy")
+        subprocess.run([sys.executable, "-c", code, path], check=True, env=dict(os.environ, SMX_INVERT_PIPELINE=pipeline), timeout=300)
+        res.append(np.load(path))
+        os.remove(path)
+    assert res[0].shape == res[1].shape == (2, 39 * 512) and res[1].dtype == np.float32
+    check_fast(res[1], res[0], "one tile per workgroup vs pipeline")
+
+
+def test_invert_fused_2048_quarter_hop_beyond_the_hand_laid_kernels():
+    """fft 2048 / hop 512 with more clips than the hand-laid synthesis kernels index (lead > 524287): the Stockham frames kernel with
+    the overlap-add fused, istft_stockham_frames_kernel<11, 16, 4>.  524288 one-frame spectra (eight distinct ones, repeated), 512
+    samples each: the first eight against the oracle, every repetition the same bits."""
+    import torch
+    rng = np.random.default_rng(11)
+    z8 = (rng.standard_normal((8, 1025, 1)) + 1j * rng.standard_normal((8, 1025, 1))).astype(np.complex64)
+    c, o = Stft.Config.create(fft_size=2048, hop=512, alignment="left"), O.stft_config(2048, hop=512, alignment="left")
+    got = Stft.invert(c, torch.from_numpy(z8).cuda().repeat(65536, 1, 1), 512)
+    assert got.is_cuda and tuple(got.shape) == (524288, 512)
+    check_fast(got[:8].cpu().numpy(), O.invert(o, z8, 512), "first eight")
+    assert torch.equal(got.reshape(65536, 8, 512), got[:8].reshape(1, 8, 512).expand(65536, -1, -1))
+
+
+@pytest.mark.parametrize("fft,hop", [(8192, 2048)])
+def test_invert_large_powers_of_two(fft, hop):
+    """Past the Stockham frames kernels (fft 512 .. 4096): istft_frames_kernel -- radix-2 passes in LDS for complex64 spectra, the
+    direct inverse DFT for complex128 ones (whose passes no longer fit the LDS)."""
+    rng = np.random.default_rng(fft)
+    z = rng.standard_normal((2, fft // 2 + 1, 7)) + 1j * rng.standard_normal((2, fft // 2 + 1, 7))
+    c, o = Stft.Config.create(fft_size=fft, hop=hop), O.stft_config(fft, hop=hop)
+    np.testing.assert_allclose(Stft.invert(c, z), O.invert(o, z, None), rtol=1e-9, atol=1e-11)
+    z32 = z.astype(np.complex64)
+    check_fast(Stft.invert(c, z32), O.invert(o, z32, None), "float32")
 
 
 def test_invert_round_trip_and_device_path():
