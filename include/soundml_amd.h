@@ -81,6 +81,15 @@ extern "C" {
  * float64 audio always uses the float64 interior. */
 #define SMX_INTERIOR_F32 0
 #define SMX_INTERIOR_F64 1
+/* Resample.quality (resample.ml:519-526): 100 / 126 / 175 dB at passband 0.913, or `Custom {attenuation; passband} */
+#define SMX_RESAMPLE_FAST 0
+#define SMX_RESAMPLE_HIGH 1
+#define SMX_RESAMPLE_BEST 2
+#define SMX_RESAMPLE_CUSTOM 3
+/* what runs the one stage of a Resample.Config (smx_resample_config_executor) */
+#define SMX_RESAMPLE_IDENTITY 0
+#define SMX_RESAMPLE_OLS 1
+#define SMX_RESAMPLE_DIRECT 2
 
 typedef struct smx_stft_config smx_stft_config;
 typedef struct smx_mel_config smx_mel_config;
@@ -89,6 +98,8 @@ typedef struct smx_stft_kernel smx_stft_kernel;
 typedef struct smx_fir_plan smx_fir_plan;
 typedef struct smx_resample_stage smx_resample_stage;
 typedef struct smx_resample_kernel smx_resample_kernel;
+typedef struct smx_resample_config smx_resample_config;
+typedef struct smx_resample_stream smx_resample_stream;
 
 /* ---- library ------------------------------------------------------------ */
 const char *smx_last_error(void);      /* message of the last failing call on this thread */
@@ -545,6 +556,7 @@ int smx_resample_shape_c128_dev(const double *d_x, const double *d_h, double *d_
 int smx_resample_stage_create(const double *proto /* 2 K L + 1 */, int64_t l, int64_t m, int64_t k, smx_resample_stage **out);
 void smx_resample_stage_destroy(smx_resample_stage *s);
 int64_t smx_resample_stage_out_length(const smx_resample_stage *s, int64_t n);       /* ceil(n L / M) */
+int smx_resample_stage_streams(const smx_resample_stage *s);   /* 1: runs as polyphase blocks, so smx_resample_kernel_prepare takes it */
 int smx_resample_stage_apply_f32(const smx_resample_stage *s, const float *x, int64_t channels, int64_t n, float *y);
 int smx_resample_stage_apply_f32_dev(const smx_resample_stage *s, const float *d_x, int64_t channels, int64_t n,
                                      int64_t x_stride, float *d_y, int64_t y_stride, void *stream);
@@ -560,6 +572,67 @@ int smx_resample_kernel_flush_f32(smx_resample_kernel *k, float *y, int64_t y_st
 int smx_resample_kernel_step_f32_dev(smx_resample_kernel *k, const float *d_x, int64_t n, int64_t x_stride, float *d_y,
                                      int64_t y_stride, int64_t *n_out, void *stream);
 int smx_resample_kernel_flush_f32_dev(smx_resample_kernel *k, float *d_y, int64_t y_stride, int64_t *n_out, void *stream);
+
+/* ---- Resample.Config / Resample.apply: arbitrary-ratio conversion (resample.mli:91-197) -----------------------------
+ * smx_resample_config_create    resample.ml:872-939 `Config.create`: validation in the reference's order and wording
+ *                               (sample_rate, target, attenuation in [40, 200], passband in [0.5, 0.99]); g = gcd,
+ *                               L = target / g, M = sample_rate / g; L = M = 1 is the identity (latency 0, no filter);
+ *                               otherwise the single-stage design of :919-932 (width (1 - passband) / max(L, M),
+ *                               kaiser_numtaps :113-116, K = max(1, ceil((taps - 1) / 2 L)), fc mid-transition, Kaiser
+ *                               beta) on smx_resample_prototype.  A bank of L (2 K + 1) 8 bytes over the 8 MiB budget
+ *                               (:230, :924-925) is SMX_INVALID_ARGUMENT with the message of :997-1011, clock-drift
+ *                               hint included.  attenuation / passband are read for SMX_RESAMPLE_CUSTOM only.  No
+ *                               device is needed.  DEVIATION: every conversion is ONE stage; the two-stage cascade
+ *                               search (`plan_cascade`, :540-870) is not restated, so the ratios the reference
+ *                               cascades run its `cost_single` design here: same spec, another latency.
+ * smx_resample_config_executor  SMX_RESAMPLE_OLS exactly for a pure x2..4 or /2..4 stage (:951) that
+ *                               smx_resample_ols_geom reports eligible: the polyphase-block stage above on this
+ *                               prototype (smx_resample_config_stage; owned by the config).  SMX_RESAMPLE_DIRECT for
+ *                               every other ratio: the polyphase dot product of :1318-1326, 2 K + 1 multiply-adds per
+ *                               output, float32 bank (rounded once, uploaded per device on first use).
+ * smx_resample_config_*         sample_rate, target, quality (:1021-1025); l / m = `rate` (:1027); latency = K in input
+ *                               samples (:1029); output_latency = K L / M reduced (:1031-1036); output_frames =
+ *                               ceil(n L / M), n < 0 is SMX_INVALID_ARGUMENT (:1038-1051); prototype: a float64 copy,
+ *                               prototype_length = 2 K L + 1 long (:1053-1056); design: the stage's (fc, beta).
+ * smx_resample_apply_f32[_dev]  `Resample.apply` (resample.mli:176-197, resample.ml:1318-1326) on float32: x [channels; n]
+ *                               -> y [channels; ceil(n L / M)], y[i] = sum_j bank[p_i][j] x[q_i - j], zeros outside the
+ *                               stream.  Every output is summed in one fixed order, so a batch equals its rows, a strided
+ *                               input its copy and any streaming partition the whole, bit for bit.
+ * smx_resample_stream_*         `Resample.Kernel.{prepare,step,flush,reset}` (resample.mli:270-319) of a DIRECT config: the
+ *                               last 2 K samples of every channel stay on the device; after `fed` samples in total the
+ *                               steps have emitted max(0, ceil((fed - K) L / M)) (`ready`, resample.ml:1298), flush the
+ *                               rest up to ceil(fed L / M).  Errors as smx_resample_kernel_*.  The config must outlive
+ *                               the kernel.  (An OLS config streams through smx_resample_kernel_* on its stage.)          */
+int smx_resample_config_create(int64_t sample_rate, int64_t target, int quality, double attenuation, double passband,
+                               smx_resample_config **out);
+void smx_resample_config_destroy(smx_resample_config *c);
+int64_t smx_resample_config_sample_rate(const smx_resample_config *c);
+int64_t smx_resample_config_target(const smx_resample_config *c);
+int smx_resample_config_quality(const smx_resample_config *c, double *attenuation, double *passband);   /* returns SMX_RESAMPLE_* */
+int64_t smx_resample_config_l(const smx_resample_config *c);
+int64_t smx_resample_config_m(const smx_resample_config *c);
+int64_t smx_resample_config_latency(const smx_resample_config *c);
+int smx_resample_config_executor(const smx_resample_config *c);
+const smx_resample_stage *smx_resample_config_stage(const smx_resample_config *c);   /* NULL unless SMX_RESAMPLE_OLS */
+int smx_resample_config_design(const smx_resample_config *c, double *fc, double *beta);
+int smx_resample_config_output_latency(const smx_resample_config *c, int64_t *num, int64_t *den);
+int smx_resample_config_output_frames(const smx_resample_config *c, int64_t n, int64_t *out);
+int64_t smx_resample_config_prototype_length(const smx_resample_config *c);
+int smx_resample_config_prototype(const smx_resample_config *c, double *h /* prototype_length */);
+int smx_resample_apply_f32(const smx_resample_config *c, const float *x, int64_t channels, int64_t n, float *y);
+int smx_resample_apply_f32_dev(const smx_resample_config *c, const float *d_x, int64_t channels, int64_t n, int64_t x_stride,
+                               float *d_y, int64_t y_stride, void *stream);
+int smx_resample_stream_prepare(const smx_resample_config *c, int64_t channels, int64_t max_block, smx_resample_stream **out);
+void smx_resample_stream_destroy(smx_resample_stream *k);
+int smx_resample_stream_reset(smx_resample_stream *k);
+int64_t smx_resample_stream_out_bound(const smx_resample_stream *k, int64_t n);   /* most samples per channel a step of n can emit */
+int64_t smx_resample_stream_pending(const smx_resample_stream *k);                /* samples per channel the next flush emits */
+int smx_resample_stream_step_f32(smx_resample_stream *k, const float *x, int64_t n, int64_t x_stride, float *y, int64_t y_stride,
+                                 int64_t *n_out);
+int smx_resample_stream_flush_f32(smx_resample_stream *k, float *y, int64_t y_stride, int64_t *n_out);
+int smx_resample_stream_step_f32_dev(smx_resample_stream *k, const float *d_x, int64_t n, int64_t x_stride, float *d_y,
+                                     int64_t y_stride, int64_t *n_out, void *stream);
+int smx_resample_stream_flush_f32_dev(smx_resample_stream *k, float *d_y, int64_t y_stride, int64_t *n_out, void *stream);
 
 #ifdef __cplusplus
 }

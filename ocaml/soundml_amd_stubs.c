@@ -869,3 +869,52 @@ CAMLprim value soundml_amd_resample_kernel_reset(value v_k) {
   smx_raise(smx_resample_kernel_reset(Rkernel_val(v_k)));
   CAMLreturn(Val_unit);
 }
+
+/* ---- Resample.Config / Resample.apply on single-stage plans (resample.mli:91-197, resample.ml:872-939, 1318-1326) -------------
+ * quality: 0 `Fast, 1 `High, 2 `Best, 3 `Custom (attenuation, passband).  Invalid_argument carries the reference's own text. */
+#define Rconfig_val(v) (*((smx_resample_config **)Data_custom_val(v)))
+static void rconfig_finalize(value v) { smx_resample_config_destroy(Rconfig_val(v)); }
+static struct custom_operations rconfig_ops = {"soundml.amd.resample_config", rconfig_finalize, custom_compare_default,
+                                               custom_hash_default, custom_serialize_default,
+                                               custom_deserialize_default, custom_compare_ext_default,
+                                               custom_fixed_length_default};
+CAMLprim value soundml_amd_resample_config(value v_rate, value v_target, value v_quality, value v_att, value v_pass) {
+  CAMLparam5(v_rate, v_target, v_quality, v_att, v_pass);
+  CAMLlocal1(v_handle);
+  smx_resample_config *c = NULL;
+  smx_raise(smx_resample_config_create(Long_val(v_rate), Long_val(v_target), Int_val(v_quality), Double_val(v_att), Double_val(v_pass), &c));
+  v_handle = caml_alloc_custom_mem(&rconfig_ops, sizeof(smx_resample_config *),
+                                   (mlsize_t)(8 * smx_resample_config_prototype_length(c)));
+  Rconfig_val(v_handle) = c;
+  CAMLreturn(v_handle);
+}
+/* (L, M, K) of the plan */
+CAMLprim value soundml_amd_resample_config_plan(value v_c) {
+  CAMLparam1(v_c);
+  CAMLlocal1(v_plan);
+  const smx_resample_config *c = Rconfig_val(v_c);
+  v_plan = caml_alloc_tuple(3);
+  Store_field(v_plan, 0, Val_long(smx_resample_config_l(c)));
+  Store_field(v_plan, 1, Val_long(smx_resample_config_m(c)));
+  Store_field(v_plan, 2, Val_long(smx_resample_config_latency(c)));
+  CAMLreturn(v_plan);
+}
+/* planar [channels; n] -> [channels; ceil(n L / M)], float32 */
+CAMLprim value soundml_amd_resample_apply(value v_c, value v_x, value v_y, value v_channels, value v_n) {
+  CAMLparam5(v_c, v_x, v_y, v_channels, v_n);
+  const smx_resample_config *c = Rconfig_val(v_c);
+  const int64_t channels = Long_val(v_channels), n = Long_val(v_n);
+  if (ba_kind(v_x) != CAML_BA_FLOAT32 || ba_kind(v_y) != CAML_BA_FLOAT32) caml_failwith("soundml_amd: unsupported dtype");
+  int64_t n_out = 0;
+  smx_raise(smx_resample_config_output_frames(c, n, &n_out));
+  if (channels < 0 || ba_dim(v_x) < channels * n || ba_dim(v_y) < channels * n_out)
+    caml_failwith("soundml_amd: buffer extents disagree with geometry");
+  const float *x = (const float *)Caml_ba_data_val(v_x);
+  float *y = (float *)Caml_ba_data_val(v_y);
+  int status;
+  caml_release_runtime_system();
+  status = smx_resample_apply_f32(c, x, channels, n, y);
+  caml_acquire_runtime_system();
+  smx_raise(status);
+  CAMLreturn(Val_unit);
+}

@@ -110,6 +110,16 @@ external resample_kernel_step_c :
 
 external resample_kernel_reset_c : rkernel_handle -> unit = "soundml_amd_resample_kernel_reset"
 
+type rconfig_handle
+
+external resample_config_c : int -> int -> int -> float -> float -> rconfig_handle = "soundml_amd_resample_config"
+
+external resample_config_plan_c : rconfig_handle -> int * int * int = "soundml_amd_resample_config_plan"
+
+external resample_apply_c :
+  rconfig_handle -> (float, Bigarray.float32_elt) flat -> (float, Bigarray.float32_elt) flat -> int -> int -> unit
+  = "soundml_amd_resample_apply"
+
 
 (* ---- helpers ---------------------------------------------------------------------------------------------------- *)
 
@@ -584,4 +594,39 @@ module Resample_kernel = struct
   let flush (k : t) = emit k (flat (Nx.zeros Nx.float32 [|1|])) 0 true
 
   let reset (k : t) = resample_kernel_reset_c k.h
+end
+
+(* [Resample.apply] on the device for the plans that are ONE stage (resample.ml:919-939: every plan the cascade search does
+   not split).  The library restates [Config.create]'s validation and single-stage design, so the body that replaces
+   [apply] (resample.ml:1318-1326 and its executors) for float32 input of such a plan is: build the device config once per
+   reference config (same rates, same quality), check that it planned the same (L, M, K), run.  A plan of two stages, and
+   float64 input, stay on the reference's own path. *)
+module Resample_config = struct
+  type t = {h: rconfig_handle; l: int; m: int; k: int}
+
+  let create ?(quality = `High) ~sample_rate ~target () =
+    let kind, att, pass =
+      match quality with
+      | `Fast -> (0, 0., 0.)
+      | `High -> (1, 0., 0.)
+      | `Best -> (2, 0., 0.)
+      | `Custom (attenuation, passband) -> (3, attenuation, passband)
+    in
+    let h = resample_config_c sample_rate target kind att pass in
+    let l, m, k = resample_config_plan_c h in
+    {h; l; m; k}
+
+  (* true when the reference planned the same single stage: its [rate] and [latency] *)
+  let same_plan (c : t) ~l ~m ~latency = c.l = l && c.m = m && c.k = latency
+
+  let apply (c : t) x =
+    if c.l = 1 && c.m = 1 then x
+    else begin
+      let batch, n = split_last x in
+      let channels = product batch in
+      let n_out = ((n * c.l) + c.m - 1) / c.m in
+      let out = Nx.zeros Nx.float32 (Array.append batch [|n_out|]) in
+      if channels > 0 && n_out > 0 then resample_apply_c c.h (flat x) (flat_out out) channels n ;
+      out
+    end
 end

@@ -2,7 +2,7 @@
 spectrogram, mel filterbank, FIR block convolution) behind the reference's own
 module names:
 
-    from soundml_amd import Stft, Mel, Chroma, Hpss, Window, Fir, mel_spectrogram, mfcc, chroma_stft, spectral_centroid
+    from soundml_amd import Stft, Mel, Chroma, Hpss, Window, Fir, Resample, resample, mel_spectrogram, mfcc, chroma_stft, spectral_centroid
 
 Everything computes in hand-written HIP kernels (gfx950) behind the C ABI of
 ``include/soundml_amd.h``; this package is the thin host mirror of
@@ -16,6 +16,8 @@ from . import mel as Mel
 from . import window as Window
 from . import fir as Fir
 from . import resample as Resample
+from .resample import resample      # (the flat function takes the package attribute; the module is Resample)
+from .resample import Spec
 from . import chroma as Chroma
 from . import convert as Convert
 from .features import mel_spectrogram, mfcc, chroma_stft, power_to_db, amplitude_to_db
@@ -65,6 +67,6 @@ def get_devices():
     return [int(arr[i]) for i in range(n.value)]
 
 
-__all__ = ["Stft", "Mel", "Chroma", "Convert", "Window", "Fir", "Resample", "mel_spectrogram", "mfcc", "chroma_stft", "power_to_db", "amplitude_to_db", "spectral_centroid",
+__all__ = ["Stft", "Mel", "Chroma", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "power_to_db", "amplitude_to_db", "spectral_centroid",
            "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

@@ -205,6 +205,7 @@ SIGNATURES = {
     "smx_resample_stage_create": (cint, [vp, i64, i64, i64, C.POINTER(vp)]),
     "smx_resample_stage_destroy": (None, [vp]),
     "smx_resample_stage_out_length": (i64, [vp, i64]),
+    "smx_resample_stage_streams": (cint, [vp]),
     "smx_resample_stage_apply_f32": (cint, [vp, vp, i64, i64, vp]),
     "smx_resample_stage_apply_f32_dev": (cint, [vp, vp, i64, i64, i64, vp, i64, vp]),
     "smx_resample_kernel_prepare": (cint, [vp, i64, i64, C.POINTER(vp)]),
@@ -216,6 +217,32 @@ SIGNATURES = {
     "smx_resample_kernel_flush_f32": (cint, [vp, vp, i64, pi64]),
     "smx_resample_kernel_step_f32_dev": (cint, [vp, vp, i64, i64, vp, i64, pi64, vp]),
     "smx_resample_kernel_flush_f32_dev": (cint, [vp, vp, i64, pi64, vp]),
+    "smx_resample_config_create": (cint, [i64, i64, cint, f64, f64, C.POINTER(vp)]),
+    "smx_resample_config_destroy": (None, [vp]),
+    "smx_resample_config_sample_rate": (i64, [vp]),
+    "smx_resample_config_target": (i64, [vp]),
+    "smx_resample_config_quality": (cint, [vp, pf64, pf64]),
+    "smx_resample_config_l": (i64, [vp]),
+    "smx_resample_config_m": (i64, [vp]),
+    "smx_resample_config_latency": (i64, [vp]),
+    "smx_resample_config_executor": (cint, [vp]),
+    "smx_resample_config_stage": (vp, [vp]),
+    "smx_resample_config_design": (cint, [vp, pf64, pf64]),
+    "smx_resample_config_output_latency": (cint, [vp, pi64, pi64]),
+    "smx_resample_config_output_frames": (cint, [vp, i64, pi64]),
+    "smx_resample_config_prototype_length": (i64, [vp]),
+    "smx_resample_config_prototype": (cint, [vp, vp]),
+    "smx_resample_apply_f32": (cint, [vp, vp, i64, i64, vp]),
+    "smx_resample_apply_f32_dev": (cint, [vp, vp, i64, i64, i64, vp, i64, vp]),
+    "smx_resample_stream_prepare": (cint, [vp, i64, i64, C.POINTER(vp)]),
+    "smx_resample_stream_destroy": (None, [vp]),
+    "smx_resample_stream_reset": (cint, [vp]),
+    "smx_resample_stream_out_bound": (i64, [vp, i64]),
+    "smx_resample_stream_pending": (i64, [vp]),
+    "smx_resample_stream_step_f32": (cint, [vp, vp, i64, i64, vp, i64, pi64]),
+    "smx_resample_stream_flush_f32": (cint, [vp, vp, i64, pi64]),
+    "smx_resample_stream_step_f32_dev": (cint, [vp, vp, i64, i64, vp, i64, pi64, vp]),
+    "smx_resample_stream_flush_f32_dev": (cint, [vp, vp, i64, pi64, vp]),
     "smx_fir_kaiser_beta": (cint, [f64, pf64]),
     "smx_fir_design_lowpass": (cint, [i64, f64, f64, vp]),
     "smx_fir_plan_create": (cint, [vp, i64, C.POINTER(vp)]),

@@ -1411,6 +1411,7 @@ int smx_resample_stage_create(const double *proto, int64_t l, int64_t m, int64_t
 }
 void smx_resample_stage_destroy(smx_resample_stage *s) { delete s; }
 int64_t smx_resample_stage_out_length(const smx_resample_stage *s, int64_t n) { return s && n >= 0 ? stage_out_length(*s, n) : -1; }
+int smx_resample_stage_streams(const smx_resample_stage *s) { return s && s->poly ? 1 : 0; }
 
 int smx_resample_stage_apply_f32_dev(const smx_resample_stage *s, const float *d_x, int64_t channels, int64_t n,
                                      int64_t x_stride, float *d_y, int64_t y_stride, void *stream) {
