@@ -458,6 +458,59 @@ int smx_hpss_f32_dev(const smx_stft_config *c, const float *d_x, int64_t lead, i
                      int64_t kernel_p, double power, double margin_h, double margin_p, float *d_y_h, float *d_y_p,
                      void *stream);
 
+/* ---- Effects: phase vocoder, time stretch, pitch shift (effects.ml, effects.mli:137-254) -------------------
+ * The phase vocoder maps a complex spectrum z [lead; bins; frames] (the layout smx_stft_transform writes) to
+ * [lead; bins; count], count = frames == 0 ? 0 : ceil(frames / rate) (effects.ml:90-92).  Output frame i sits at analysis
+ * position i * rate: magnitudes interpolated between frames i0 = trunc(i * rate) and i0 + 1, phase an accumulator
+ * advanced per output frame by omega_k + pv(arg z[k, i0 + 1] - arg z[k, i0] - omega_k) (effects.ml:189-229); the two rows
+ * past the end read as silence.  SMX_PHASE_LOCKED adds identity phase locking (effects.ml:146-182).  The arithmetic is
+ * float64 in the reference's operation order whatever the dtype of z and whatever smx_set_interior says, rounded once
+ * into the dtype of z.  Only fft_size and hop of the stft config are read; bins must be fft_size / 2 + 1.  The locked
+ * mode holds one frame's bins in LDS: up to 4083 bins (fft 8164), SMX_FAILURE beyond.
+ *
+ * smx_phase_vocoder_frames    effects.ml:90-92   the output frame count; no device
+ * smx_time_stretch_length     effects.ml:295     rint(n / rate), ties to even; no device
+ * smx_semitones               effects.ml:345-386 the best rational num/den for 2^(n / bins_per_octave) with neither term
+ *                                                above 512: denominators 1..512, error compared in log2, the first best
+ *                                                kept, reduced; no device
+ * smx_phase_vocoder_*         effects.ml:285-289 `phase_vocoder`: checks of :96-117 (rate finite and positive, the bin axis)
+ * smx_time_stretch_*          effects.ml:291-298 `time_stretch`: x [lead; n] -> y [lead; rint(n / rate)]: Stft.transform ->
+ *                                                vocoder -> Stft.invert ~length, bit for bit those three calls, the
+ *                                                spectra on the device in clip chunks.  float64 audio, and float32 audio
+ *                                                under SMX_INTERIOR_F64 (widened first, rounded once at the end), keep
+ *                                                complex128 spectra between the stages.  Also raises what Stft.invert
+ *                                                raises (stft.ml:745-786).
+ * smx_pitch_shift_*           effects.ml:324-334 `pitch_shift`: r is the resample config built for num -> den
+ *                                                (smx_resample_config_create(num, den, ...)): time_stretch at the very
+ *                                                quotient (double)den / (double)num, Resample.apply, cut or zero-extended
+ *                                                to n.  DEVIATION: the conversion is float32 (smx_resample_apply_f32);
+ *                                                float64 audio is stretched in float64, converted in float32, widened.  */
+#define SMX_PHASE_INDEPENDENT 0
+#define SMX_PHASE_LOCKED 1
+int smx_phase_vocoder_frames(int64_t frames, double rate, int64_t *count);
+int smx_time_stretch_length(int64_t n, double rate, int64_t *length);
+int smx_semitones(double n, int64_t bins_per_octave, int64_t *num, int64_t *den);
+int smx_phase_vocoder_c64(const smx_stft_config *c, const float *z_c64, int64_t lead, int64_t bins, int64_t frames,
+                          double rate, int phase, float *out_c64);
+int smx_phase_vocoder_c128(const smx_stft_config *c, const double *z_c128, int64_t lead, int64_t bins, int64_t frames,
+                           double rate, int phase, double *out_c128);
+int smx_phase_vocoder_c64_dev(const smx_stft_config *c, const float *d_z_c64, int64_t lead, int64_t bins, int64_t frames,
+                              double rate, int phase, float *d_out_c64, void *stream);
+int smx_phase_vocoder_c128_dev(const smx_stft_config *c, const double *d_z_c128, int64_t lead, int64_t bins,
+                               int64_t frames, double rate, int phase, double *d_out_c128, void *stream);
+int smx_time_stretch_f32(const smx_stft_config *c, const float *x, int64_t lead, int64_t n, double rate, int phase,
+                         float *y);
+int smx_time_stretch_f64(const smx_stft_config *c, const double *x, int64_t lead, int64_t n, double rate, int phase,
+                         double *y);
+int smx_time_stretch_f32_dev(const smx_stft_config *c, const float *d_x, int64_t lead, int64_t n, double rate, int phase,
+                             float *d_y, void *stream);
+int smx_pitch_shift_f32(const smx_stft_config *c, const smx_resample_config *r, int phase, const float *x, int64_t lead,
+                        int64_t n, float *y);
+int smx_pitch_shift_f64(const smx_stft_config *c, const smx_resample_config *r, int phase, const double *x, int64_t lead,
+                        int64_t n, double *y);
+int smx_pitch_shift_f32_dev(const smx_stft_config *c, const smx_resample_config *r, int phase, const float *d_x,
+                            int64_t lead, int64_t n, float *d_y, void *stream);
+
 /* ---- Chroma over a linear-frequency spectrum (chroma.ml:95-317; Soundml.chroma_stft, soundml.ml:97-107) --
  * Config: the float64 [n_chroma; bins] projection of chroma.ml:109-175 (Gaussian bumps in the wrapped
  * chroma distance, unit euclidean columns, optional octave envelope, rows rolled so row 0 is C).

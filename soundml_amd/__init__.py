@@ -25,6 +25,8 @@ from .spectral import (spectral_centroid, spectral_bandwidth, spectral_rolloff, 
                        spectral_centroid_stage, spectral_bandwidth_stage, spectral_rolloff_stage, spectral_flatness_stage)
 from . import hpss as Hpss
 from .hpss import hpss_masks, hpss_of_spectrogram, hpss_of_stft, hpss, harmonic, percussive
+from . import effects as Effects
+from .effects import phase_vocoder, time_stretch, pitch_shift, semitones
 from . import shard
 
 
@@ -68,5 +70,5 @@ def get_devices():
 
 
 __all__ = ["Stft", "Mel", "Chroma", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "power_to_db", "amplitude_to_db", "spectral_centroid",
-           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
+           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

@@ -131,6 +131,19 @@ SIGNATURES = {
     "smx_hpss_f32": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_f64": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_f32_dev": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
+    "smx_phase_vocoder_frames": (cint, [i64, f64, C.POINTER(i64)]),
+    "smx_time_stretch_length": (cint, [i64, f64, C.POINTER(i64)]),
+    "smx_semitones": (cint, [f64, i64, C.POINTER(i64), C.POINTER(i64)]),
+    "smx_phase_vocoder_c64": (cint, [vp, vp, i64, i64, i64, f64, cint, vp]),
+    "smx_phase_vocoder_c128": (cint, [vp, vp, i64, i64, i64, f64, cint, vp]),
+    "smx_phase_vocoder_c64_dev": (cint, [vp, vp, i64, i64, i64, f64, cint, vp, vp]),
+    "smx_phase_vocoder_c128_dev": (cint, [vp, vp, i64, i64, i64, f64, cint, vp, vp]),
+    "smx_time_stretch_f32": (cint, [vp, vp, i64, i64, f64, cint, vp]),
+    "smx_time_stretch_f64": (cint, [vp, vp, i64, i64, f64, cint, vp]),
+    "smx_time_stretch_f32_dev": (cint, [vp, vp, i64, i64, f64, cint, vp, vp]),
+    "smx_pitch_shift_f32": (cint, [vp, vp, cint, vp, i64, i64, vp]),
+    "smx_pitch_shift_f64": (cint, [vp, vp, cint, vp, i64, i64, vp]),
+    "smx_pitch_shift_f32_dev": (cint, [vp, vp, cint, vp, i64, i64, vp, vp]),
     "smx_chroma_config_create": (cint, [i64, f64, f64, cint, f64, cint, i64, i64, C.POINTER(vp)]),
     "smx_chroma_config_destroy": (None, [vp]),
     "smx_chroma_config_n_chroma": (i64, [vp]),

@@ -567,4 +567,93 @@ smx_chroma_config *chroma_config_create(int64_t n_chroma, double tuning, double 
   return cfg;
 }
 
+
+// ---- Effects: the host-only arithmetic (effects.ml:66-123, 290-296, 345-386) ------------------------------------------------
+namespace {
+const char *g_text(double v, char (&buffer)[40]) {   // "%g" as OCaml prints it: a NaN has no sign
+  std::snprintf(buffer, sizeof buffer, "%g", std::isnan(v) ? std::fabs(v) : v);
+  return buffer;
+}
+}  // namespace
+
+void check_stretch_rate(const char *op, double rate) {   // effects.ml:96-102
+  char text[40];
+  if (!(std::isfinite(rate) && rate > 0.0))
+    throw InvalidArgument(format("%s: cannot stretch by a rate of %s (the rate must be finite and positive)", op, g_text(rate, text)));
+}
+
+int64_t pvoc_out_frames(int64_t frames, double rate) {   // effects.ml:90-92: the positions i * rate strictly below frames
+  if (frames <= 0) return 0;
+  const double count = std::ceil((double)frames / rate);
+  if (!(count < 4611686018427387904.0)) throw Failure("phase_vocoder: the output frame count does not fit 62 bits");
+  return (int64_t)count;
+}
+
+int64_t stretch_length(int64_t n, double rate) {   // effects.ml:295: n / rate rounded to nearest, ties to even
+  const double length = std::nearbyint((double)n / rate);
+  if (!(length < 4611686018427387904.0)) throw Failure("time_stretch: the output length does not fit 62 bits");
+  return (int64_t)length;
+}
+
 }  // namespace smx
+
+extern "C" {
+
+int smx_phase_vocoder_frames(int64_t frames, double rate, int64_t *count) {
+  return smx::guarded([&] {
+    smx::check_stretch_rate("phase_vocoder", rate);
+    if (frames < 0) throw smx::Failure("phase_vocoder: negative extent");
+    if (!count) throw smx::Failure("phase_vocoder: null result pointer");
+    *count = smx::pvoc_out_frames(frames, rate);
+  });
+}
+
+int smx_time_stretch_length(int64_t n, double rate, int64_t *length) {
+  return smx::guarded([&] {
+    smx::check_stretch_rate("time_stretch", rate);
+    if (n < 0) throw smx::Failure("time_stretch: negative extent");
+    if (!length) throw smx::Failure("time_stretch: null result pointer");
+    *length = smx::stretch_length(n, rate);
+  });
+}
+
+int smx_semitones(double n, int64_t bins_per_octave, int64_t *num, int64_t *den) {
+  using namespace smx;
+  return guarded([&] {   // effects.ml:345-386
+    constexpr int64_t cap = 512;
+    char text[40];
+    if (bins_per_octave < 1)
+      throw InvalidArgument(format("semitones: cannot divide the octave into %lld steps (bins_per_octave must be at least 1)",
+                                   (long long)bins_per_octave));
+    if (!std::isfinite(n))
+      throw InvalidArgument(format("semitones: cannot shift by %s steps (the step count must be finite)", g_text(n, text)));
+    if (!num || !den) throw Failure("semitones: null result pointer");
+    const double target = std::pow(2.0, n / (double)bins_per_octave);
+    bool found = false;
+    double best_error = 0.0;
+    int64_t best_num = 0, best_den = 0;
+    for (int64_t d = 1; d <= cap; ++d) {   // for a fixed denominator the nearest numerator is the rounded product: exhaustive
+      const double r = std::nearbyint(target * (double)d);
+      if (!(r >= 1.0 && r <= (double)cap)) continue;
+      const double error = std::fabs(std::log2(r / (double)d) - std::log2(target));
+      if (found && best_error <= error) continue;   // the first best is kept
+      found = true;
+      best_error = error;
+      best_num = (int64_t)r;
+      best_den = d;
+    }
+    if (!found)
+      throw InvalidArgument(format("semitones: cannot represent a frequency ratio of %s within %lld (the step count is too far from unity)",
+                                   g_text(target, text), (long long)cap));
+    int64_t a = best_num, b = best_den;
+    while (b) {
+      const int64_t t = a % b;
+      a = b;
+      b = t;
+    }
+    *num = best_num / a;
+    *den = best_den / a;
+  });
+}
+
+}  // extern "C"

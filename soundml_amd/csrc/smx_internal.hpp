@@ -429,6 +429,23 @@ struct HpssJob {
 void launch_hpss(const HpssJob &job);             // hpss.hip
 bool hpss_takes_fast_path(const HpssJob &job);    // the 31 x 31 float32 tile kernel serves the job (else: the general one)
 
+// Effects.phase_vocoder (effects.ml:184-274) over a device-resident complex stack [lead; bins; frames] -> [lead; bins; count]:
+// float64 inside whatever the element width, one rounding into it
+struct PvocJob {
+  const void *z = nullptr;       // device, interleaved complex
+  int elem_bytes = 4;            // component width: 4 = complex64, 8 = complex128
+  int64_t lead = 0, bins = 0, frames = 0, count = 0;
+  int64_t fft_size = 0, hop = 0;
+  double rate = 1.0;
+  bool locked = false;           // identity phase locking (effects.ml:146-182)
+  void *out = nullptr;           // device [lead; bins; count], element type of z
+  hipStream_t stream = nullptr;
+};
+void launch_pvoc(const PvocJob &job);             // effects.hip
+void check_stretch_rate(const char *op, double rate);     // effects.ml:96-102 (host_config.cpp)
+int64_t pvoc_out_frames(int64_t frames, double rate);     // effects.ml:90-92
+int64_t stretch_length(int64_t n, double rate);           // effects.ml:295
+
 // Chroma.apply (chroma.ml:285-317): float64 projection + per-frame normalisation, one rounding
 struct ChromaJob {
   const smx_chroma_config *config = nullptr;
