@@ -368,7 +368,7 @@ __device__ __forceinline__ typename vec2_of<S>::type *mixed_transform(typename v
 #ifdef SMX_STAMPS
 // Diagnostic build only (make STAMPS=1): per-phase cycle sums of every wave, read back with
 // smx_debug_read_stamps().  Never compiled into the shipped library; no output depends on it.
-constexpr int kStampSlots = 24;
+constexpr int kStampSlots = 32;
 __device__ unsigned long long g_stamp_sums[4096 * 16 * kStampSlots];
 #ifdef SMX_STAMPS_COARSE
 // only the whole-loop clock check (slots 20 / 21: shader cycles and 100 MHz reference ticks around the tile loop):

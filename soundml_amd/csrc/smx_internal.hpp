@@ -45,7 +45,7 @@ void set_last_error(const std::string &message);
   } while (0)
 
 // ---- environment switches ------------------------------------------------------------------------------------------
-// The shipped library reads thirteen variables, each once per use and parsed ONE way (env_flag: unset -> -1, "0" / "" /
+// The shipped library reads fourteen variables, each once per use and parsed ONE way (env_flag: unset -> -1, "0" / "" /
 // "false" / "off" -> 0, anything else -> 1); none alters results except by selecting another kernel of the same contract:
 //   SMX_DISABLE_FAST   the generic kernels instead of the hand-laid ones (tests: two implementations of one contract)
 //   SMX_POWER_SKEW=0   fft-2048 / fft-1024 power spectrogram: the plain per-tile flush instead of whole aligned 64-byte blocks / 128-byte lines (tests, A/B timing)
@@ -55,6 +55,7 @@ void set_last_error(const std::string &message);
 //   SMX_GL_FRAME_MAJOR=0 Griffin-Lim at fft 2048 / hop 512: its rebuilt spectra in the reference layout [bin][frame] instead of frame-major (tests: bit-identical; A/B timing)
 //   SMX_WIDE_PIPELINE=0 float64 interior at fft 2048: the one-tile-per-workgroup kernel instead of the persistent one (tests: bit-identical)
 //   SMX_MEL_DENSE=1    fused mel at fft 2048: the dense 16 x 16 x 4 product instead of the banded 4 x 4 x 1 one (tests, A/B timing)
+//   SMX_FAST_BLOCKS=k  the fused STFT kernels: at most k persistent workgroups, i.e. longer tile ranges per workgroup (tests: a small request walks clip boundaries inside one range; same values)
 //   SMX_MIXED_OFF      chirp-z instead of the mixed-radix kernels (tests: the two agree)
 //   SMX_HOST_TRACE     print where a host-pointer call's time goes
 //   SMX_HOST_PIPELINE=0 host-pointer STFT calls: upload, kernels, download one after the other instead of overlapped clip units

@@ -25,6 +25,7 @@
 // mel 2048 + 4 n_mels.
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "fft_device.hpp"
 #include "smx_internal.hpp"
@@ -356,6 +357,7 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
   a.total_tiles = job.lead * tiles;
   const int cu_count = device_cu_count();   // (per device, thread-safe: tables.cpp)
   a.blocks = a.total_tiles < cu_count ? a.total_tiles : cu_count;
+  if (const long cap = env_int("SMX_FAST_BLOCKS", 0); cap > 0 && cap < a.blocks) a.blocks = cap;   // (tests: one workgroup walks many tiles of a small request)
   auto set_ranges = [&] { a.range_base = a.total_tiles / a.blocks; a.range_extra = a.total_tiles % a.blocks; };
   set_ranges();
   if (!strip && !tg.mel && !tg.complex_out && tg.border_left + tg.border_right > 0 && a.blocks < cu_count) {
@@ -511,6 +513,9 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
 #ifdef SMX_DIAG
   if (diag_flag("SMX_NOSTORE") == 1) a.abl_nostore = 1;   // timing-only ablations of the 32-lane kernel (results wrong by construction)
   a.abl_p32 = (int)diag_int("SMX_P32_ABL", 0);
+  // (bit 0: every tile reads tile 1 of clip 0, which must lie inside that clip)
+  if ((a.abl_p32 & 1) && !((p0 + kFT) * c.hop - left >= 0 && (p0 + 2 * kFT - 1) * c.hop - left + kN <= n && count >= 2 * kFT && !strip))
+    throw Failure("stft: SMX_P32_ABL=1 needs a request whose second tile lies inside the clip");
 #endif
   (void)square;
   // The power spectrogram at fft 2048: the 32-lane frame pipeline (stft_fast_p32.hpp).

@@ -520,7 +520,7 @@ struct MelMid32 {
     }
   }
   __device__ __forceinline__ void postpass_at(int s) const {
-    if (s == SMX_P32_LOAD_AT) load_frame32<ALIGNED>(src_border ? src_clip : src, lane & 31, raw);
+    if (s == SMX_P32_LOAD_AT) load_frame32<ALIGNED, SMX_P32_ORDER_SHARED != 0>(src_border ? src_clip : src, lane & 31, raw, (wave & 1) != 0);
     if (s == 15 && src_border) load_frame32_padded(a, src_clip, (int)(src - src_clip), lane & 31, raw);   // (wave-uniform; see PowerMid32::load_next)
   }
 };

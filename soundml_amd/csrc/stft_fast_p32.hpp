@@ -343,6 +343,7 @@ __device__ __forceinline__ void frame32_to_tile(const FastArgs &a, const Lane32 
 #if SMX_P32_WAIT0
   // the samples were requested most of a tile ago: one wait for all of them instead of one per product (a wait is an issue slot)
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+  mid.template stamp<24>();             // (stamps builds: the wait alone, from the loop top's stamp<0> on)
 #endif
   f2 e[16], o[16];
   float4 winE[8];
@@ -571,15 +572,44 @@ __device__ __forceinline__ void frame32_to_tile(const FastArgs &a, const Lane32 
 
 // raw samples of the lane's frame: z[n] = (x[2n], x[2n+1]), n = l + 32 j; `src` is the frame's first sample (per lane:
 // the two halves of a wave read different frames)
-template <bool ALIGNED>
-__device__ __forceinline__ void load_frame32(const float *src, int l, float2 (&raw)[32]) {
+// BY_PARITY (the power kernel): waves w and w + 1 read frames 4096 bytes apart, so element j of wave w + 1 is element j + 16 of wave
+// w.  Odd waves request elements 16..31 before 0..15 -- same registers, same addresses, two copies of the 32 requests behind a
+// wave-uniform branch -- and at every step one neighbouring pair of waves asks the L1 for the same 256 bytes instead of asking 16
+// steps and 64 KB of other lines apart: C2 0.4772 -> 0.4630 ms interleaved, A/A spread 0.0010 (profiles/r09/NOTES.md).
+#ifndef SMX_P32_ORDER
+#define SMX_P32_ORDER 1   // 0: every wave requests elements 0..31 in order (A/B builds)
+#endif
+#ifndef SMX_P32_ORDER_SHARED
+#define SMX_P32_ORDER_SHARED 0   // 1: the fused mel kernel and Stft.transform take the order too (A/B builds)
+#endif
+template <int FIRST, int... I>
+__device__ __forceinline__ void load_frame32_seq(const float2 *p, const float2 *p_hi, float2 (&raw)[32], std::integer_sequence<int, I...>) {
+  ((raw[(I + FIRST) & 31] = ((I + FIRST) & 31) < 16 ? p[32 * ((I + FIRST) & 31)] : p_hi[32 * (((I + FIRST) & 31) - 16)]), ...);
+}
+template <bool ALIGNED, bool BY_PARITY = false>
+__device__ __forceinline__ void load_frame32(const float *src, int l, float2 (&raw)[32], bool upper_first = false /* wave-uniform */) {
   if constexpr (ALIGNED) {
     const float2 *p = reinterpret_cast<const float2 *>(src) + l;
     long hi_off = 512;
     asm volatile("" : "+s"(hi_off));   // keeps ONE second base (13-bit immediates reach 16 x 256 bytes)
     const float2 *p_hi = p + hi_off;
+    if constexpr (BY_PARITY && SMX_P32_ORDER) {
+      // (into a copy, and the upper-first branch between compiler barriers: written straight into `raw` the array stays in scratch
+      // memory, and without the barriers the two branches -- the same 32 loads -- are merged into one)
+      float2 tmp[32];
+      if (upper_first) {
+        asm volatile("" ::: "memory");
+        load_frame32_seq<16>(p, p_hi, tmp, std::make_integer_sequence<int, 32>{});
+        asm volatile("" ::: "memory");
+      } else {
+        load_frame32_seq<0>(p, p_hi, tmp, std::make_integer_sequence<int, 32>{});
+      }
 #pragma unroll
-    for (int j = 0; j < 32; ++j) raw[j] = j < 16 ? p[32 * j] : p_hi[32 * (j - 16)];
+      for (int j = 0; j < 32; ++j) raw[j] = tmp[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 32; ++j) raw[j] = j < 16 ? p[32 * j] : p_hi[32 * (j - 16)];
+    }
   } else {
     const float *p = src + 2 * l;
     long hi_off = 1024;
@@ -918,7 +948,11 @@ struct PowerMid32 {
   // for border tiles, or the padding rule there, made the loop spill (9 to 37 registers; the compiler's allocation, not a
   // count of live values): this form costs one register.  The two border tiles of a clip begin a memory round trip late.
   __device__ __forceinline__ void load_next() const {
-    load_frame32<ALIGNED>(src_border ? src_clip : src, lane & 31, raw);
+    const float *from = src_border ? src_clip : src;
+#ifdef SMX_DIAG
+    if (a.abl_p32 & 1) from = src;   // (src_clip is clip 0 and src its resident frame: a border tile asks for that frame on both paths)
+#endif
+    load_frame32<ALIGNED, true>(from, lane & 31, raw, (wave & 1) != 0);
   }
   __device__ __forceinline__ void load_next_border() const {
     if (src_border) load_frame32_padded(a, src_clip, (int)(src - src_clip), lane & 31, raw);
@@ -1106,7 +1140,9 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
     const float *src = frame_ptr(src_clip, more ? ftnext : tw.ft);
     const bool src_border = tile_border(more ? ftnext : tw.ft);
 #ifdef SMX_DIAG
-    if (a.abl_p32 & 1) src = frame_ptr(a.x, 1);   // timing only: every tile reads the same resident samples
+    // timing only: every tile reads the same resident samples, tile 1 of clip 0 (inside the clip: the launcher checks).  A border
+    // tile keeps both of its request paths, each on that frame: load_frame32_padded takes its position from src - src_clip.
+    if (a.abl_p32 & 1) { src_clip = a.x; src = frame_ptr(a.x, 1); }
 #endif
     const bool have = (int64_t)tw.ft * kFT + 2 * wave < a.count;   // wave-uniform: at least the first half has a frame
     if constexpr (SKEW == 1) {
@@ -1364,7 +1400,7 @@ struct CplxMid32 {
   __device__ __forceinline__ void after_transposition_issue() const {}
   __device__ __forceinline__ void after_exchange_issue() const {}
   __device__ __forceinline__ void postpass_at(int s) const {
-    if (s == (SKEW ? 15 : SMX_P32_LOAD_AT)) load_frame32<ALIGNED>(src_border ? src_clip : src, lane & 31, raw);
+    if (s == (SKEW ? 15 : SMX_P32_LOAD_AT)) load_frame32<ALIGNED, SMX_P32_ORDER_SHARED != 0>(src_border ? src_clip : src, lane & 31, raw, (wave & 1) != 0);
     if (s == 15 && src_border) load_frame32_padded(a, src_clip, (int)(src - src_clip), lane & 31, raw);   // (wave-uniform; see PowerMid32::load_next)
   }
 };

@@ -28,7 +28,7 @@ ev = []
 for _ in range(10):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(); run(); b.record(); torch.cuda.synchronize(); ev.append(a.elapsed_time(b))
-S, nwg = 24, 256
+S, nwg = 32, 256
 buf = np.zeros(nwg * 16 * S, dtype=np.uint64)
 read = lib.smx_debug_read_stamps64 if mode == "f64" else lib.smx_debug_read_stamps
 assert read(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), buf.size) == 0

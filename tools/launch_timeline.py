@@ -16,7 +16,7 @@ lib.smx_stft_config_create.argtypes = [i64, i64, i64, ctypes.c_int, ctypes.c_int
 assert lib.smx_stft_config_create(2048, -(2**63), 512, 0, 0, 0.0, 0, 0, None, ctypes.byref(h)) == 0
 lib.smx_stft_power_range_f32_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64, ctypes.c_double, vp, vp]
 shapes = [(int(sys.argv[i]), int(sys.argv[i + 1])) for i in range(1, len(sys.argv) - 1, 2)] or [(256, 480000), (512, 1440000)]
-S, nwg = 24, 256
+S, nwg = 32, 256
 for clips, n in shapes:
     frames = 1 + n // 512
     x = torch.rand(clips, n, device="cuda") * 2 - 1

@@ -22,7 +22,7 @@ ev = []
 for _ in range(6):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); run(); e1.record(); torch.cuda.synchronize(); ev.append(e0.elapsed_time(e1))
-S, nwg = 24, 256
+S, nwg = 32, 256
 buf = np.zeros(nwg * 16 * S, dtype=np.uint64)
 assert lib.smx_debug_read_stamps64(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), buf.size) == 0
 st = buf.reshape(nwg, 16, S).astype(np.float64)[:, :8, :]

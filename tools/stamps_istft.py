@@ -22,7 +22,7 @@ ev = []
 for _ in range(8):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(); run(); b.record(); torch.cuda.synchronize(); ev.append(a.elapsed_time(b))
-S, nwg = 24, 256
+S, nwg = 32, 256
 buf = np.zeros(nwg * 16 * S, dtype=np.uint64)
 assert lib.smx_debug_read_stamps_istft(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), buf.size) == 0
 st = buf.reshape(nwg, 16, S).astype(np.float64)[:, :8, :]

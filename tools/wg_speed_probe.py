@@ -25,7 +25,7 @@ def tile_times(first):
         for _ in range(10): run(first)
         torch.cuda.synchronize()
     run(first); torch.cuda.synchronize()
-    S, nwg = 24, 256
+    S, nwg = 32, 256
     buf = np.zeros(nwg * 16 * S, dtype=np.uint64)
     assert lib.smx_debug_read_stamps(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), buf.size) == 0
     st = buf.reshape(nwg, 16, S)[:, :8, :].astype(np.int64)
