@@ -541,6 +541,75 @@ int smx_chroma_stft_f32_dev(const smx_stft_config *sc, const smx_chroma_config *
                             int64_t lead, int64_t n, int64_t x_stride, double power, int norm, double norm_p,
                             float *d_out, void *stream);
 
+/* ---- Cqt: the offline constant-Q / variable-Q transform (cqt.ml:121-692, cqt.mli:64-315) --------------------------
+ * Config (cqt.ml:287-424; no device needed): the octave-by-octave frequency ladder, relative bandwidths, fractional
+ * filter lengths, main-lobe cutoff and its Nyquist check, the early decimations and the octave plan, all in float64 with
+ * the reference's validation and Invalid_argument messages.  Octave i (highest first) holds `count` filters from global
+ * bin `first`, analysed at `hop` on the signal halved `early + halvings` times by Resample.Config.create(2, 1, `High`)
+ * through an n_fft-point rectangular centered frame.  Instead of the half-spectrum matrix K of `octave_kernel`
+ * (cqt.ml:202-247) the config keeps its time-domain form with the octave gain folded in,
+ *   g[b, n] = sum_{k <= n_fft / 2} K[b, k] exp(-2 pi i k n / n_fft),  so that  K . rfft(frame) = sum_n frame[n] g[b, n],
+ * and the device projects every frame against g in float64 with no transform (cqt.hip).
+ * gamma: SMX_CQT_GAMMA_FIXED reads gamma_value (finite, non-negative).  window / window_param as smx_window_make_param.
+ * DEVIATIONS: float32 audio only (the reference also decimates float64); the streaming Cqt.Kernel is not restated. */
+typedef struct smx_cqt_config smx_cqt_config;
+#define SMX_CQT_GAMMA_CONSTANT_Q 0
+#define SMX_CQT_GAMMA_ERB 1
+#define SMX_CQT_GAMMA_FIXED 2
+int smx_cqt_config_create(int64_t n_bins, int64_t sample_rate, double fmin, int64_t bins_per_octave, int gamma, double gamma_value,
+                          double tuning, double filter_scale, double norm, int window, double window_param, int scale, int64_t hop,
+                          int pad, double pad_value, smx_cqt_config **out);                    /* cqt.ml:287-424 */
+void smx_cqt_config_destroy(smx_cqt_config *c);
+int64_t smx_cqt_config_n_bins(const smx_cqt_config *c);                                        /* cqt.mli:145-194 */
+int64_t smx_cqt_config_bins_per_octave(const smx_cqt_config *c);
+int64_t smx_cqt_config_sample_rate(const smx_cqt_config *c);
+int64_t smx_cqt_config_hop(const smx_cqt_config *c);
+int64_t smx_cqt_config_n_octaves(const smx_cqt_config *c);
+int64_t smx_cqt_config_early(const smx_cqt_config *c);    /* 2:1 decimations before octave zero (cqt.ml:338-345) */
+int64_t smx_cqt_config_latency(const smx_cqt_config *c);  /* cqt.mli:196-231, K = smx_resample_config_latency of the 2:1 plan */
+double smx_cqt_config_cutoff(const smx_cqt_config *c);
+int smx_cqt_frequencies(const smx_cqt_config *c, double *out /* [n_bins] */);                  /* cqt.mli:243 */
+int smx_cqt_filter_lengths(const smx_cqt_config *c, double *out /* [n_bins] */);               /* cqt.mli:257 */
+int smx_cqt_frames(const smx_cqt_config *c, int64_t n, int64_t *frames);                       /* cqt.mli:278 */
+/* the plan, for inspection: octave i's extents; its taps g as [count; n_fft] interleaved (re, im) float64; the [n_bins]
+ * `scale` divisors, sqrt of the filter lengths at the rate octave zero runs at (all ones when scale is off) */
+int smx_cqt_config_octave(const smx_cqt_config *c, int64_t i, int64_t *first, int64_t *count, int64_t *n_fft, int64_t *hop,
+                          int64_t *halvings);
+int smx_cqt_config_taps(const smx_cqt_config *c, int64_t i, double *out);
+int smx_cqt_config_divisors(const smx_cqt_config *c, double *out);
+/* transform (cqt.mli:285-303): x [lead; n] float32 -> [lead; n_bins; frames] complex64 (interleaved), float64 inside,
+ * one rounding.  power_spectrum (cqt.mli:305-315): |transform|^power in float32, the magnitude taken of the rounded
+ * complex64 value as the reference does.  Zero lead or zero frames: nothing is written. */
+int smx_cqt_transform_f32(const smx_cqt_config *c, const float *x, int64_t lead, int64_t n, float *out_c64);
+int smx_cqt_transform_f32_dev(const smx_cqt_config *c, const float *d_x, int64_t lead, int64_t n, int64_t x_stride, float *d_out_c64,
+                              void *stream);
+int smx_cqt_power_spectrum_f32(const smx_cqt_config *c, const float *x, int64_t lead, int64_t n, double power, float *out);
+int smx_cqt_power_spectrum_f32_dev(const smx_cqt_config *c, const float *d_x, int64_t lead, int64_t n, int64_t x_stride, double power,
+                                   float *d_out, void *stream);
+/* diagnostics (tests of the projection kernel alone, on exact data): one launch of the strided filter-bank projection
+ *   z[c, first + b, p] = sum_{n < n_fft} src(c, p hop - n_fft / 2 + n) g[b, n] / divisor[b],   b < count, p < frames,
+ * with caller-supplied device taps d_taps [count; n_fft] (re, im) float64 and optional d_divisors [count]; src is
+ * d_x [lead; n] float32 under the boundary rule `pad` of Stft's centered alignment; the result lands in rows
+ * [first, first + count) of d_out [lead; n_bins; frames]: complex64 (as_power == 0) or |z|^power float32 */
+int smx_debug_cqt_project_f32_dev(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, const double *d_taps,
+                                  const double *d_divisors, int64_t count, int64_t n_fft, int64_t hop, int pad, double pad_value,
+                                  int64_t first, int64_t n_bins, int64_t frames, int as_power, double power, void *d_out,
+                                  void *stream);
+/* Chroma over a constant-Q spectrum (chroma.ml:324-385; Soundml.chroma_cqt).  cqt_projection: the 0/1 fold
+ * [n_chroma; n_bins] (bins_per_octave must be a multiple of n_chroma).  of_cqt: fold + the per-frame normalisation of
+ * smx_chroma_apply.  chroma_cqt = of_cqt . Cqt.power_spectrum ~power:1; the magnitudes stay on the device. */
+int smx_chroma_cqt_projection(const smx_cqt_config *c, int64_t n_chroma, double *out /* [n_chroma; n_bins] */);
+int smx_chroma_of_cqt_f32(const smx_cqt_config *c, const float *s, int64_t lead, int64_t bins, int64_t frames, int64_t n_chroma,
+                          int norm, double norm_p, float *out);
+int smx_chroma_of_cqt_f64(const smx_cqt_config *c, const double *s, int64_t lead, int64_t bins, int64_t frames, int64_t n_chroma,
+                          int norm, double norm_p, double *out);
+int smx_chroma_of_cqt_f32_dev(const smx_cqt_config *c, const float *d_s, int64_t lead, int64_t bins, int64_t frames, int64_t n_chroma,
+                              int norm, double norm_p, float *d_out, void *stream);
+int smx_chroma_cqt_f32(const smx_cqt_config *c, const float *x, int64_t lead, int64_t n, int64_t n_chroma, int norm, double norm_p,
+                       float *out);
+int smx_chroma_cqt_f32_dev(const smx_cqt_config *c, const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t n_chroma,
+                           int norm, double norm_p, float *d_out, void *stream);
+
 /* ---- Least-squares synthesis: Stft.invert (stft.ml:902-939, stft.mli "invert") --------------------
  * x[m] = (sum_p w[m - p hop] irfft(Z[:, p])[m - p hop]) / (sum_p w^2[m - p hop]) in padded coordinates,
  * boundary extension trimmed, cut or zero-extended to `length`.  z is [lead; bins; frames] complex

@@ -2,7 +2,7 @@
 spectrogram, mel filterbank, FIR block convolution) behind the reference's own
 module names:
 
-    from soundml_amd import Stft, Mel, Chroma, Hpss, Window, Fir, Resample, resample, mel_spectrogram, mfcc, chroma_stft, spectral_centroid
+    from soundml_amd import Stft, Mel, Chroma, Cqt, Hpss, Window, Fir, Resample, resample, mel_spectrogram, mfcc, chroma_stft, chroma_cqt, spectral_centroid
 
 Everything computes in hand-written HIP kernels (gfx950) behind the C ABI of
 ``include/soundml_amd.h``; this package is the thin host mirror of
@@ -19,8 +19,9 @@ from . import resample as Resample
 from .resample import resample      # (the flat function takes the package attribute; the module is Resample)
 from .resample import Spec
 from . import chroma as Chroma
+from . import cqt as Cqt
 from . import convert as Convert
-from .features import mel_spectrogram, mfcc, chroma_stft, power_to_db, amplitude_to_db
+from .features import mel_spectrogram, mfcc, chroma_stft, chroma_cqt, power_to_db, amplitude_to_db
 from .spectral import (spectral_centroid, spectral_bandwidth, spectral_rolloff, spectral_flatness,
                        spectral_centroid_stage, spectral_bandwidth_stage, spectral_rolloff_stage, spectral_flatness_stage)
 from . import hpss as Hpss
@@ -69,6 +70,6 @@ def get_devices():
     return [int(arr[i]) for i in range(n.value)]
 
 
-__all__ = ["Stft", "Mel", "Chroma", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "power_to_db", "amplitude_to_db", "spectral_centroid",
+__all__ = ["Stft", "Mel", "Chroma", "Cqt", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "chroma_cqt", "power_to_db", "amplitude_to_db", "spectral_centroid",
            "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

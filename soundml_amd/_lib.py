@@ -156,6 +156,33 @@ SIGNATURES = {
     "smx_chroma_stft_f32": (cint, [vp, vp, vp, i64, i64, f64, cint, f64, vp]),
     "smx_chroma_stft_f64": (cint, [vp, vp, vp, i64, i64, f64, cint, f64, vp]),
     "smx_chroma_stft_f32_dev": (cint, [vp, vp, vp, i64, i64, i64, f64, cint, f64, vp, vp]),
+    "smx_cqt_config_create": (cint, [i64, i64, f64, i64, cint, f64, f64, f64, f64, cint, f64, cint, i64, cint, f64, C.POINTER(vp)]),
+    "smx_cqt_config_destroy": (None, [vp]),
+    "smx_cqt_config_n_bins": (i64, [vp]),
+    "smx_cqt_config_bins_per_octave": (i64, [vp]),
+    "smx_cqt_config_sample_rate": (i64, [vp]),
+    "smx_cqt_config_hop": (i64, [vp]),
+    "smx_cqt_config_n_octaves": (i64, [vp]),
+    "smx_cqt_config_early": (i64, [vp]),
+    "smx_cqt_config_latency": (i64, [vp]),
+    "smx_cqt_config_cutoff": (f64, [vp]),
+    "smx_cqt_frequencies": (cint, [vp, vp]),
+    "smx_cqt_filter_lengths": (cint, [vp, vp]),
+    "smx_cqt_frames": (cint, [vp, i64, pi64]),
+    "smx_cqt_config_octave": (cint, [vp, i64, pi64, pi64, pi64, pi64, pi64]),
+    "smx_cqt_config_taps": (cint, [vp, i64, vp]),
+    "smx_cqt_config_divisors": (cint, [vp, vp]),
+    "smx_cqt_transform_f32": (cint, [vp, vp, i64, i64, vp]),
+    "smx_cqt_transform_f32_dev": (cint, [vp, vp, i64, i64, i64, vp, vp]),
+    "smx_cqt_power_spectrum_f32": (cint, [vp, vp, i64, i64, f64, vp]),
+    "smx_cqt_power_spectrum_f32_dev": (cint, [vp, vp, i64, i64, i64, f64, vp, vp]),
+    "smx_debug_cqt_project_f32_dev": (cint, [vp, i64, i64, i64, vp, vp, i64, i64, i64, cint, f64, i64, i64, i64, cint, f64, vp, vp]),
+    "smx_chroma_cqt_projection": (cint, [vp, i64, vp]),
+    "smx_chroma_of_cqt_f32": (cint, [vp, vp, i64, i64, i64, i64, cint, f64, vp]),
+    "smx_chroma_of_cqt_f64": (cint, [vp, vp, i64, i64, i64, i64, cint, f64, vp]),
+    "smx_chroma_of_cqt_f32_dev": (cint, [vp, vp, i64, i64, i64, i64, cint, f64, vp, vp]),
+    "smx_chroma_cqt_f32": (cint, [vp, vp, i64, i64, i64, cint, f64, vp]),
+    "smx_chroma_cqt_f32_dev": (cint, [vp, vp, i64, i64, i64, i64, cint, f64, vp, vp]),
     "smx_stft_kernel_prepare_power": (cint, [vp, cint, i64, i64, f64, C.POINTER(vp)]),
     "smx_stft_stage_latency": (i64, [vp]),
     "smx_stft_frame_bound": (i64, [vp, i64]),

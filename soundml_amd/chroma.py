@@ -5,8 +5,11 @@
     y = Chroma.apply(c, s, norm="inf")                                # [...; bins; frames] -> [...; n_chroma; frames]
 
 The float64 projection matrix is built once on the host (chroma.ml:109-175); the product and the per-frame
-normalisation run in float64 on the device with one rounding to the dtype of ``s``.  The constant-Q side of
-the reference's module (``of_cqt``) is out of scope: there is no CQT here.
+normalisation run in float64 on the device with one rounding to the dtype of ``s``.  The constant-Q side
+(chroma.ml:324-385) folds the bins of a ``Cqt.Config`` onto pitch classes with a 0/1 matrix:
+
+    w = Chroma.cqt_projection(np.float64, cqt_config, n_chroma=12)    # [n_chroma; n_bins]
+    y = Chroma.of_cqt(cqt_config, Cqt.power_spectrum(cqt_config, x, power=1.0))
 """
 from __future__ import annotations
 
@@ -111,4 +114,42 @@ def apply(c: Config, s, norm="inf"):
         return out
     fn = lib.smx_chroma_apply_f32 if b.bytes == 4 else lib.smx_chroma_apply_f64
     check(fn(c._h, b.ptr(), lead, bins, frames, kind, p, out_ptr(out)))
+    return b.wrap(out)
+
+
+def cqt_projection(dtype, c, n_chroma: int = 12) -> np.ndarray:
+    """``Chroma.cqt_projection dtype ?n_chroma c`` (chroma.ml:332-369): the 0/1 assignment ``[n_chroma; n_bins]`` of the bins of
+    the ``Cqt.Config`` ``c`` to pitch classes; ``bins_per_octave`` must be a multiple of ``n_chroma``."""
+    n_chroma = int(n_chroma)
+    out = np.empty((max(n_chroma, 0), c.n_bins), dtype=np.float64)
+    check(lib.smx_chroma_cqt_projection(c._h, n_chroma, C.c_void_p(out.ctypes.data)))
+    return out.astype(dtype)
+
+
+def of_cqt(c, s, n_chroma: int = 12, norm="inf"):
+    """``Chroma.of_cqt ?n_chroma ?norm c s`` (chroma.ml:371-385): constant-Q magnitudes ``[...; n_bins; frames]`` ->
+    ``[...; n_chroma; frames]``: the fold, then the per-frame normalisation of ``apply``."""
+    kind, p = norm_args(norm)
+    n_chroma = int(n_chroma)
+    # the norm's and the resolution's conditions come before the tensor is looked at (chroma.ml:372-374): let the ABI word them
+    check(lib.smx_chroma_of_cqt_f32(c._h, None, 0, c.n_bins, 0, n_chroma, kind, p, None))
+    nd = len(s.shape)
+    if nd < 2:
+        raise _lib.InvalidArgument("of_cqt: cannot project a rank-%d tensor (the projection needs [...; bins; frames])" % nd)
+    b = Batch(s, "of_cqt")
+    bins, frames = int(b.shape[-2]), int(b.shape[-1])
+    lead_shape = b.shape[:-2]
+    lead = prod(lead_shape)
+    if bins != c.n_bins:
+        check(lib.smx_chroma_of_cqt_f32(c._h, None, lead, bins, frames, n_chroma, kind, p, None))
+    out = b.empty(lead_shape + (n_chroma, frames))
+    if b.device:
+        if b.bytes != 4:
+            raise _lib.Failure("of_cqt: device-resident float64 spectrograms are not supported; pass a host array")
+        with b.device_guard():
+            check(lib.smx_chroma_of_cqt_f32_dev(c._h, b.ptr(), lead, bins, frames, n_chroma, kind, p,
+                                                out_ptr(out) if out.numel() else None, b.stream()))
+        return out
+    fn = lib.smx_chroma_of_cqt_f32 if b.bytes == 4 else lib.smx_chroma_of_cqt_f64
+    check(fn(c._h, b.ptr(), lead, bins, frames, n_chroma, kind, p, out_ptr(out) if out.size else None))
     return b.wrap(out)

@@ -231,6 +231,37 @@ struct smx_chroma_config {
   mutable std::map<int, double *> tables_;
 };
 
+// Cqt.Config.t (cqt.ml:71-112): the octave plan in float64, built once on the host (cqt_plan.cpp); cqt.hip owns the device side
+struct smx_cqt_config {
+  struct Octave {                // cqt.ml:78-85, highest octave first
+    int64_t first = 0, count = 0, n_fft = 0, hop = 0, halvings = 0;
+    std::vector<double> taps;    // [count; n_fft] (re, im): the half-spectrum kernel's time-domain form, octave gain folded in
+  };
+  double fmin = 0.0, gamma_value = 0.0, tuning = 0.0, filter_scale = 1.0, norm = 1.0, window_param = 0.0, pad_value = 0.0;
+  int64_t bins_per_octave = 12, hop = 512, n_bins = 0, sample_rate = 0, n_octaves = 0, early = 0;
+  int gamma = SMX_CQT_GAMMA_CONSTANT_Q, window = SMX_WINDOW_HANN, pad = SMX_PAD_CONSTANT;
+  bool scale = true;
+  std::vector<double> freqs, alphas, gammas, lengths;   // [n_bins]; lengths at sample_rate
+  std::vector<double> divisors;                          // [n_bins] sqrt of the lengths at the base rate; ones when scale is off
+  double cutoff = 0.0;
+  std::vector<Octave> octaves;
+  smx_resample_config *half = nullptr;                   // the one exact 1/2 conversion plan (cqt.ml:417)
+  int64_t frames(int64_t n) const;                       // cqt.ml:546-556
+  int64_t latency() const;                               // cqt.ml:471-479
+
+  struct Tables {                // per device: one buffer per octave, taps [count; n_fft] double2 then divisors [count]
+    std::vector<double *> octaves;
+  };
+  const Tables &tables() const;                                  // cqt.hip
+  const double *fold(int64_t n_chroma) const;                    // cqt.hip: the 0/1 fold transposed [n_bins; rows_pad] on the current device
+  ~smx_cqt_config();                                             // cqt.hip
+
+ private:
+  mutable std::mutex mutex_;
+  mutable std::map<int, Tables> tables_;
+  mutable std::map<std::pair<int, int64_t>, double *> folds_;
+};
+
 namespace smx {
 
 // ---- host <-> device transfers of the host-pointer entry points (transfer.cpp) ----
@@ -264,6 +295,11 @@ smx_mel_config *mel_config_create(int64_t n_mels, int64_t sample_rate, int64_t f
                                   double f_min, bool has_f_max, double f_max, int scale, int norm);
 smx_chroma_config *chroma_config_create(int64_t n_chroma, double tuning, double ctroct, bool has_octwidth,
                                         double octwidth, bool base_c, int64_t sample_rate, int64_t fft_size);
+smx_cqt_config *cqt_config_create(int64_t n_bins, int64_t sample_rate, double fmin, int64_t bins_per_octave, int gamma,
+                                  double gamma_value, double tuning, double filter_scale, double norm, int window, double window_param,
+                                  bool scale, int64_t hop, int pad, double pad_value);          // cqt_plan.cpp (cqt.ml:287-424)
+// the 0/1 fold [n_chroma; n_bins] of chroma.ml:332-366, its conditions raised under `op` (cqt_plan.cpp)
+std::vector<double> cqt_fold_matrix(const char *op, const smx_cqt_config &c, int64_t n_chroma);
 bool stft_nola(const smx_stft_config &c);                                        // stft.ml:731-743
 int64_t stft_output_length(const smx_stft_config &c, int64_t frames);            // stft.ml:792-796
 // envelope over the span of `frames` frames as three pieces: positions [0, head) and [stop, span) summed tap by
@@ -450,6 +486,9 @@ int64_t stretch_length(int64_t n, double rate);           // effects.ml:295
 // Chroma.apply (chroma.ml:285-317): float64 projection + per-frame normalisation, one rounding
 struct ChromaJob {
   const smx_chroma_config *config = nullptr;
+  // without a config (Chroma.of_cqt): the projection itself, device [bins; n_chroma rounded up to a multiple of 12] float64
+  const double *weights_t = nullptr;
+  int64_t bins = 0, n_chroma = 0;
   const void *s = nullptr;       // device [lead; bins; frames]
   int elem_bytes = 4;
   int64_t lead = 0, frames = 0;
@@ -459,6 +498,26 @@ struct ChromaJob {
   hipStream_t stream = nullptr;
 };
 void launch_chroma(const ChromaJob &job);       // spectral.hip
+
+// One octave of Cqt.transform (cqt.ml:648-649 with the divisors of :659-665): the strided filter-bank projection
+//   z[c, first + b, p] = sum_{n < n_fft} src(c, p hop - n_fft / 2 + n) g[b, n] / divisor[b]
+// in float64 over float32 samples, rounded once into rows [first, first + count) of out [lead; n_bins; frames]
+struct CqtProjectJob {
+  const float *x = nullptr;        // device [lead; n] with x_stride
+  int64_t lead = 0, n = 0, x_stride = 0;
+  const double *taps = nullptr;    // device [count; n_fft] (re, im)
+  const double *divisors = nullptr;   // device [count], or null
+  int64_t count = 0, n_fft = 0, hop = 0;
+  int pad = SMX_PAD_CONSTANT;      // Stft's centered alignment: positions outside [0, n)
+  double pad_value = 0.0;
+  double gain = 1.0;               // multiplies every sum before the divisor (the octave recursion's scalars)
+  int64_t first = 0, n_bins = 0, frames = 0;
+  OutMode mode = OUT_COMPLEX;      // complex64, or |z|^power in float32
+  double power = 2.0;
+  void *out = nullptr;
+  hipStream_t stream = nullptr;
+};
+void launch_cqt_project(const CqtProjectJob &job);   // cqt.hip
 
 struct MelSpecJob {
   StftJob stft;                  // out/out_stride unused; mode/power used

@@ -298,26 +298,26 @@ bool launch_spectral(const SpectralJob &job) {
 }
 
 void launch_chroma(const ChromaJob &job) {
-  const smx_chroma_config &c = *job.config;
   if (job.lead <= 0 || job.frames <= 0) return;
+  const int64_t n_chroma = job.config ? job.config->n_chroma : job.n_chroma;
   ChromaArgs a{};
   a.s = job.s;
   a.out = job.out;
-  a.wt = c.device_weights();
+  a.wt = job.config ? job.config->device_weights() : job.weights_t;
   a.lead = job.lead;
-  a.bins = c.bins();
+  a.bins = job.config ? job.config->bins() : job.bins;
   a.frames = job.frames;
   a.ftiles = (job.frames + 255) / 256;
-  a.n_chroma = (int)c.n_chroma;
-  a.rows_pad = (c.n_chroma + kChromaChunk - 1) / kChromaChunk * kChromaChunk;
+  a.n_chroma = (int)n_chroma;
+  a.rows_pad = (n_chroma + kChromaChunk - 1) / kChromaChunk * kChromaChunk;
   a.norm = job.norm;
   a.norm_p = job.norm_p;
   a.inv_p = job.norm == SMX_CHROMA_NORM_P ? 1.0 / job.norm_p : 1.0;
   a.tiny = job.elem_bytes == 8 ? DBL_MIN : (double)FLT_MIN;   // chroma.ml:42-55 smallest_normal
   const int64_t blocks = a.lead * a.ftiles;
-  const int64_t chunks = (c.n_chroma + kChromaChunk - 1) / kChromaChunk;
+  const int64_t chunks = (n_chroma + kChromaChunk - 1) / kChromaChunk;
   if (blocks > 2147483647LL || chunks > 65535) throw Failure("chroma: too many tiles for one launch");
-  SMX_HIP_CHECK(smx::pool_malloc_async((void **)&a.raw, (size_t)job.lead * (size_t)c.n_chroma * (size_t)job.frames * sizeof(double),
+  SMX_HIP_CHECK(smx::pool_malloc_async((void **)&a.raw, (size_t)job.lead * (size_t)n_chroma * (size_t)job.frames * sizeof(double),
                                job.stream));
   if (job.elem_bytes == 8) {
     SMX_LAUNCH(chroma_project_kernel<double>, dim3((unsigned)blocks, (unsigned)chunks), dim3(256), 0, job.stream, a);

@@ -88,6 +88,28 @@ def chroma_stft(stft_config, chroma_config, x, power: float = 2.0, norm="inf"):
     return b.wrap(out)
 
 
+def chroma_cqt(cqt_config, x, n_chroma: int = 12, norm="inf"):
+    """``Soundml.chroma_cqt cqt ?n_chroma ?norm x`` = Chroma.of_cqt ?n_chroma ?norm cqt (Cqt.power_spectrum ~power:1. cqt x);
+    [...; n] float32 -> [...; n_chroma; frames].  The magnitudes never leave the device."""
+    from . import chroma as Chroma
+    from . import cqt as Cqt
+    kind, p = Chroma.norm_args(norm)
+    n_chroma = int(n_chroma)
+    check(lib.smx_chroma_of_cqt_f32(cqt_config._h, None, 0, cqt_config.n_bins, 0, n_chroma, kind, p, None))   # the norm, the resolution
+    b = Cqt._batch("power_spectrum", x)
+    n = int(b.shape[-1])
+    lead_shape = b.shape[:-1]
+    lead = prod(lead_shape)
+    out = b.empty(lead_shape + (n_chroma, Cqt.frames(cqt_config, n)))
+    if b.device:
+        with b.device_guard():
+            check(lib.smx_chroma_cqt_f32_dev(cqt_config._h, b.ptr(), lead, n, max(n, 1), n_chroma, kind, p,
+                                             out_ptr(out) if out.numel() else None, b.stream()))
+        return out
+    check(lib.smx_chroma_cqt_f32(cqt_config._h, b.ptr(), lead, n, n_chroma, kind, p, out_ptr(out) if out.size else None))
+    return b.wrap(out)
+
+
 def _to_db(which, s, reference, amin, top_db):
     if not hasattr(s, "shape"):
         import numpy as np
