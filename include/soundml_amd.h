@@ -551,7 +551,7 @@ int smx_chroma_stft_f32_dev(const smx_stft_config *sc, const smx_chroma_config *
  *   g[b, n] = sum_{k <= n_fft / 2} K[b, k] exp(-2 pi i k n / n_fft),  so that  K . rfft(frame) = sum_n frame[n] g[b, n],
  * and the device projects every frame against g in float64 with no transform (cqt.hip).
  * gamma: SMX_CQT_GAMMA_FIXED reads gamma_value (finite, non-negative).  window / window_param as smx_window_make_param.
- * DEVIATIONS: float32 audio only (the reference also decimates float64); the streaming Cqt.Kernel is not restated. */
+ * DEVIATION: float32 audio only (the reference also decimates float64).  The streaming face is smx_cqt_kernel_* below. */
 typedef struct smx_cqt_config smx_cqt_config;
 #define SMX_CQT_GAMMA_CONSTANT_Q 0
 #define SMX_CQT_GAMMA_ERB 1
@@ -595,6 +595,45 @@ int smx_debug_cqt_project_f32_dev(const float *d_x, int64_t lead, int64_t n, int
                                   const double *d_divisors, int64_t count, int64_t n_fft, int64_t hop, int pad, double pad_value,
                                   int64_t first, int64_t n_bins, int64_t frames, int as_power, double power, void *d_out,
                                   void *stream);
+/* ---- Cqt.Kernel: the streaming transform (cqt.mli:317-413, cqt.ml:694-1012) ------------------------------------------
+ * One state for all channels: a streaming 2:1 decimator (smx_resample_stream_*) per early decimation and per halving
+ * octave, per octave a device ring of its float32 stream, and one ring of finished columns.  The law is stronger than the
+ * reference's (which anchors on the kernel's own one-chunk run and documents 2e-6 against the offline transform): the
+ * concatenation of every step's columns plus the flush's equals smx_cqt_transform_f32 (with a power:
+ * smx_cqt_power_spectrum_f32) of the concatenated signal BIT FOR BIT under every chunking, because the projection is one
+ * fixed fma chain per (frame, bin) whichever kernel runs it and the decimator is bit-equal to its offline face.
+ * The schedule is host arithmetic and needs no device:
+ *   columns_ready  the columns that have left once `fed` samples went in (cqt.mli:199-231): frame p of octave i is projected
+ *                  when its stream holds p hop_i + n_fft_i / 2 samples (one more for frame 0 under Reflect, which reads the
+ *                  mirror of its first sample); a column leaves when every octave has projected it.  For Constant and Edge
+ *                  padding this is max(0, (fed - latency) / hop + 1).
+ *   column_bound   the most columns one step of at most max_block samples, or the flush, returns.
+ *   run_ahead      the most columns an octave can be ahead of the slowest one (cqt.mli:381-383); the column ring holds
+ *                  run_ahead + column_bound. */
+typedef struct smx_cqt_kernel smx_cqt_kernel;
+int smx_cqt_config_columns_ready(const smx_cqt_config *c, int64_t fed, int64_t *columns);
+int smx_cqt_config_column_bound(const smx_cqt_config *c, int64_t max_block, int64_t *bound);
+int smx_cqt_config_run_ahead(const smx_cqt_config *c, int64_t *columns);
+/* prepare (cqt.mli:370-388): Invalid_argument for channels < 1 or max_block < 1, checked before any device is touched.
+ * has_power != 0: the kernel emits |z|^power in float32 instead of complex64.  The config must outlive the kernel. */
+int smx_cqt_kernel_prepare(const smx_cqt_config *c, int64_t channels, int64_t max_block, int has_power, double power,
+                           smx_cqt_kernel **out);
+void smx_cqt_kernel_destroy(smx_cqt_kernel *k);
+int smx_cqt_kernel_reset(smx_cqt_kernel *k);                                                    /* cqt.mli:411-412 */
+/* host arithmetic: the columns a step of n samples would return now, and what the flush would (size the output by them) */
+int64_t smx_cqt_kernel_columns_after(const smx_cqt_kernel *k, int64_t n);
+int64_t smx_cqt_kernel_pending(const smx_cqt_kernel *k);
+/* step (cqt.mli:390-400): x [channels; n] float32 with x_stride; the completed columns land in out [channels; n_bins;
+ * out_stride] (complex64 interleaved, or float32 under a power) and *columns says how many.  Invalid_argument: a drained
+ * kernel, n > max_block.  n = 0 does nothing.  The _dev form enqueues on `stream` and never synchronises.
+ * flush (cqt.mli:402-409): drains the decimators front to back, projects the remaining frames under the right boundary
+ * rule and returns every column up to smx_cqt_frames of the total; a second flush returns none. */
+int smx_cqt_kernel_step_f32(smx_cqt_kernel *k, const float *x, int64_t n, int64_t x_stride, void *out, int64_t out_stride,
+                            int64_t *columns);
+int smx_cqt_kernel_flush_f32(smx_cqt_kernel *k, void *out, int64_t out_stride, int64_t *columns);
+int smx_cqt_kernel_step_f32_dev(smx_cqt_kernel *k, const float *d_x, int64_t n, int64_t x_stride, void *d_out, int64_t out_stride,
+                                int64_t *columns, void *stream);
+int smx_cqt_kernel_flush_f32_dev(smx_cqt_kernel *k, void *d_out, int64_t out_stride, int64_t *columns, void *stream);
 /* Chroma over a constant-Q spectrum (chroma.ml:324-385; Soundml.chroma_cqt).  cqt_projection: the 0/1 fold
  * [n_chroma; n_bins] (bins_per_octave must be a multiple of n_chroma).  of_cqt: fold + the per-frame normalisation of
  * smx_chroma_apply.  chroma_cqt = of_cqt . Cqt.power_spectrum ~power:1; the magnitudes stay on the device. */

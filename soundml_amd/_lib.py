@@ -176,6 +176,18 @@ SIGNATURES = {
     "smx_cqt_transform_f32_dev": (cint, [vp, vp, i64, i64, i64, vp, vp]),
     "smx_cqt_power_spectrum_f32": (cint, [vp, vp, i64, i64, f64, vp]),
     "smx_cqt_power_spectrum_f32_dev": (cint, [vp, vp, i64, i64, i64, f64, vp, vp]),
+    "smx_cqt_config_columns_ready": (cint, [vp, i64, pi64]),
+    "smx_cqt_config_column_bound": (cint, [vp, i64, pi64]),
+    "smx_cqt_config_run_ahead": (cint, [vp, pi64]),
+    "smx_cqt_kernel_prepare": (cint, [vp, i64, i64, cint, f64, C.POINTER(vp)]),
+    "smx_cqt_kernel_destroy": (None, [vp]),
+    "smx_cqt_kernel_reset": (cint, [vp]),
+    "smx_cqt_kernel_columns_after": (i64, [vp, i64]),
+    "smx_cqt_kernel_pending": (i64, [vp]),
+    "smx_cqt_kernel_step_f32": (cint, [vp, vp, i64, i64, vp, i64, pi64]),
+    "smx_cqt_kernel_flush_f32": (cint, [vp, vp, i64, pi64]),
+    "smx_cqt_kernel_step_f32_dev": (cint, [vp, vp, i64, i64, vp, i64, pi64, vp]),
+    "smx_cqt_kernel_flush_f32_dev": (cint, [vp, vp, i64, pi64, vp]),
     "smx_debug_cqt_project_f32_dev": (cint, [vp, i64, i64, i64, vp, vp, i64, i64, i64, cint, f64, i64, i64, i64, cint, f64, vp, vp]),
     "smx_chroma_cqt_projection": (cint, [vp, i64, vp]),
     "smx_chroma_of_cqt_f32": (cint, [vp, vp, i64, i64, i64, i64, cint, f64, vp]),

@@ -12,8 +12,16 @@ between octaves by ``Resample.Config.create(2, 1, "high")`` while the octave's h
 centered rectangular analysis is projected against the bank in float64 (one kernel launch per octave, one rounding).  Host
 arrays give host arrays; device tensors stay on the device.
 
-DEVIATIONS: float32 audio only -- float64 raises, as ``Resample.apply`` does (the reference decimates either); the streaming
-``Cqt.Kernel`` is not restated.
+    k = Cqt.Kernel.prepare(c, channels=2, max_block=4096)          # the streaming face (cqt.mli:317-413)
+    cols = [k.step(chunk) for chunk in chunks] + [k.flush()]         # None, or [...; n_bins; columns]; together: transform, bit for bit
+
+``Cqt.Kernel`` holds one state for all channels on the device: the streaming 2:1 decimators, each octave's recent samples and a
+ring of finished columns.  A column leaves in the step that completes its last octave (``columns_ready``); ``flush`` drains the
+decimators and applies the right boundary rule.  The concatenation of every step plus flush equals ``transform`` (with
+``power``: ``power_spectrum``) of the concatenated signal bit for bit under every chunking -- stronger than the reference, whose
+two paths sum in different orders and agree to 2e-6.
+
+DEVIATION: float32 audio only -- float64 raises, as ``Resample.apply`` does (the reference decimates either).
 """
 from __future__ import annotations
 
@@ -196,3 +204,105 @@ def power_spectrum(c: Config, x, power: float = 2.0):
     return _run("power_spectrum", c, x, False,
                 lambda x_, lead, n, out: lib.smx_cqt_power_spectrum_f32(c._h, x_, lead, n, power, out),
                 lambda x_, lead, n, stride, out, stream: lib.smx_cqt_power_spectrum_f32_dev(c._h, x_, lead, n, stride, power, out, stream))
+
+
+# ---- Cqt.Kernel: the streaming transform (cqt.mli:317-413) ------------------------------------------------------------------
+
+def _count(fn, *args) -> int:
+    out = C.c_int64()
+    check(fn(*args, C.byref(out)))
+    return out.value
+
+
+def columns_ready(c: Config, fed: int) -> int:
+    """The columns a ``Kernel`` has returned once ``fed`` samples went in (cqt.mli:199-231): host arithmetic, no device.  A column
+    leaves when every octave has projected it; for constant and edge padding that is ``max(0, (fed - latency) // hop + 1)``,
+    under reflect an octave's frame 0 waits for one sample more (it reads the mirror of its first)."""
+    return _count(lib.smx_cqt_config_columns_ready, c._h, int(fed))
+
+
+def column_bound(c: Config, max_block: int) -> int:
+    """The most columns one ``step`` of at most ``max_block`` samples, or ``flush``, returns."""
+    return _count(lib.smx_cqt_config_column_bound, c._h, int(max_block))
+
+
+def run_ahead(c: Config) -> int:
+    """The most columns an octave can be ahead of the slowest one; the kernel's column ring holds ``run_ahead + column_bound``."""
+    return _count(lib.smx_cqt_config_run_ahead, c._h)
+
+
+class Kernel:
+    """``Cqt.Kernel`` (cqt.ml:694-1012): ``prepare``, ``step``, ``flush``, ``reset``.  Chunks are float32 ``[...; m]`` whose leading
+    axes multiply to ``channels``, host arrays or device tensors (then everything is enqueued on torch's current stream and
+    nothing synchronises); ``step`` / ``flush`` return ``[...; n_bins; columns]`` complex64 -- float32 ``|z|^power`` when prepared
+    with a ``power`` -- or ``None``.  Mutable, single-owner; the config outlives it."""
+
+    def __init__(self, handle, c, channels, max_block, power):
+        self._h, self._c, self.channels, self.max_block, self.power = handle, c, channels, max_block, power
+        self._device, self._torch, self._lead = None, False, (channels,)
+
+    @staticmethod
+    def prepare(c: Config, channels: int, max_block: int, power=None) -> "Kernel":
+        handle = C.c_void_p()
+        check(lib.smx_cqt_kernel_prepare(c._h, int(channels), int(max_block), 0 if power is None else 1,
+                                         2.0 if power is None else float(power), C.byref(handle)))
+        return Kernel(handle, c, int(channels), int(max_block), None if power is None else float(power))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and lib is not None:
+            try:
+                lib.smx_cqt_kernel_destroy(h)
+            except Exception:
+                pass
+
+    latency = property(lambda self: self._c.latency, doc="cqt.mli:196-231, in input samples")
+    column_bound = property(lambda self: column_bound(self._c, self.max_block))
+
+    def _empty(self, columns, device=None):
+        shape = self._lead + (self._c.n_bins, columns)
+        if device is not None:
+            import torch
+            return torch.empty(shape, dtype=torch.complex64 if self.power is None else torch.float32, device=device)
+        return np.zeros(shape, dtype=np.complex64 if self.power is None else np.float32)
+
+    def step(self, chunk):
+        b = _batch("step", chunk)
+        lead, m = b.shape[:-1], int(b.shape[-1])
+        if prod(lead) != self.channels:
+            raise _lib.InvalidArgument("step: cannot analyse %d channels (the kernel was prepared for %d)" % (prod(lead), self.channels))
+        columns = max(0, lib.smx_cqt_kernel_columns_after(self._h, m))
+        got = C.c_int64()
+        self._lead, self._torch = lead, b.torch
+        if b.device:
+            self._device = b.data.device
+            out = self._empty(columns, self._device) if columns else None
+            with b.device_guard():
+                check(lib.smx_cqt_kernel_step_f32_dev(self._h, b.ptr(), m, max(m, 1), out_ptr(out) if columns else None, columns,
+                                                      C.byref(got), b.stream()))
+            return out
+        out = self._empty(columns) if columns else None
+        check(lib.smx_cqt_kernel_step_f32(self._h, b.ptr(), m, max(m, 1), out_ptr(out) if columns else None, columns, C.byref(got)))
+        return b.wrap(out) if columns else None
+
+    def flush(self):
+        """The withheld columns (None when there are none, and on a second flush); on the device if the stream was fed from it."""
+        columns = max(0, lib.smx_cqt_kernel_pending(self._h))
+        got = C.c_int64()
+        if self._device is not None:
+            import torch
+            out = self._empty(columns, self._device) if columns else None
+            with torch.cuda.device(self._device):
+                stream = C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+                check(lib.smx_cqt_kernel_flush_f32_dev(self._h, out_ptr(out) if columns else None, columns, C.byref(got), stream))
+            return out
+        out = self._empty(columns) if columns else None
+        check(lib.smx_cqt_kernel_flush_f32(self._h, out_ptr(out) if columns else None, columns, C.byref(got)))
+        if out is not None and self._torch:
+            import torch
+            return torch.from_numpy(out)
+        return out
+
+    def reset(self) -> None:
+        self._device, self._torch = None, False
+        check(lib.smx_cqt_kernel_reset(self._h))

@@ -18,16 +18,12 @@
 // reference's composition with one float32 rounding fewer per stage, and no elementwise pass over the signal.
 #include <cfloat>
 
-#include "smx_internal.hpp"
-#include "stft_sample.hpp"
+#include "cqt_project.hpp"
 
 namespace smx {
 namespace {
 
-constexpr int kTapTile = 32;               // taps per LDS tile
-constexpr int kFrameTile = 128;            // frames per workgroup: 32 thread groups x 4
-constexpr int kBinTile = 16;               // bins per workgroup: 8 thread lanes x 2
-constexpr int kRowPad = kTapTile + 1;      // doubles per frame row where frames do not share samples (33: conflict-free reads)
+constexpr int kTapTile = kCqtTapTile, kFrameTile = kCqtFrameTile, kBinTile = kCqtBinTile, kRowPad = kCqtRowPad;   // cqt_project.hpp
 
 struct CqtArgs {
   const float *x;
@@ -74,24 +70,7 @@ __global__ void __launch_bounds__(256) cqt_project_kernel(CqtArgs a) {
       }
     }
     __syncthreads();
-    const double *sx = s_x + fg * fs;
-    auto tap = [&](int j) {
-      const double2 t0 = s_taps[j * kBinTile + bl], t1 = s_taps[j * kBinTile + bl + 8];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double v = sx[r * 32 * fs + j];
-        re[r][0] = fma(v, t0.x, re[r][0]);
-        im[r][0] = fma(v, t0.y, im[r][0]);
-        re[r][1] = fma(v, t1.x, re[r][1]);
-        im[r][1] = fma(v, t1.y, im[r][1]);
-      }
-    };
-    if (tn == kTapTile) {
-#pragma unroll 8
-      for (int j = 0; j < kTapTile; ++j) tap(j);
-    } else {
-      for (int j = 0; j < tn; ++j) tap(j);
-    }
+    cqt_tile_fma(s_taps, s_x + fg * fs, fs, tn, bl, re, im);
     __syncthreads();
   }
 #pragma unroll
@@ -102,15 +81,8 @@ __global__ void __launch_bounds__(256) cqt_project_kernel(CqtArgs a) {
     for (int h = 0; h < 2; ++h) {
       const int64_t b = b0 + bl + 8 * h;
       if (b >= a.count) continue;
-      double zr = re[r][h] * a.gain, zi = im[r][h] * a.gain;
-      if (a.divisors) {
-        const double d = a.divisors[b];
-        zr /= d;
-        zi /= d;
-      }
       const int64_t at = (clip * a.n_bins + a.first + b) * a.frames + p0 + f;
-      if (a.mode == OUT_COMPLEX) reinterpret_cast<float2 *>(a.out)[at] = make_float2((float)zr, (float)zi);
-      else reinterpret_cast<float *>(a.out)[at] = magnitude_pow<double, float>(zr, zi, a.power);
+      cqt_finish(re[r][h], im[r][h], a.gain, a.divisors, b, a.mode, a.power, a.out, at);
     }
   }
 }

@@ -327,3 +327,52 @@ int64_t smx_cqt_config::latency() const {   // cqt.ml:471-479: max over octaves 
   }
   return worst;
 }
+
+// ---- the streaming schedule (Cqt.Kernel, cqt.ml:694-1012): host integers only, cqt_stream.hip runs by them -----------------------
+namespace smx {
+
+namespace {
+// resample.ml:1298 `ready` of the 2:1 plan: the outputs whose every input is among the first `fed` samples
+int64_t halved_ready(int64_t fed, int64_t lag) { return fed > lag ? (fed - lag + 1) / 2 : 0; }
+int64_t ceil_div_pos(int64_t a, int64_t b) { return a <= 0 ? 0 : (a + b - 1) / b; }
+}  // namespace
+
+// frames of octave `o` whose every sample is among the first `seen` of its stream: frame p ends at p hop + n_fft - n_fft / 2.
+// Under Reflect frame 0 also reads sample n_fft / 2 (the mirror of its first), so nothing is ready before seen > n_fft / 2
+// (the install threshold left_width + 1 of stft.ml:447-452).
+int64_t cqt_octave_ready(const smx_cqt_config &c, const smx_cqt_config::Octave &o, int64_t seen) {
+  const int64_t reach = o.n_fft - o.n_fft / 2;
+  if (seen < reach || (c.pad == SMX_PAD_REFLECT && seen < o.n_fft / 2 + 1)) return 0;
+  return (seen - reach) / o.hop + 1;
+}
+
+// columns every octave has produced once `fed` samples went in: the chain of 2:1 stages, then the slowest octave
+int64_t cqt_columns_ready(const smx_cqt_config &c, int64_t fed) {
+  const int64_t lag = smx_resample_config_latency(c.half);
+  int64_t least = INT64_MAX, level = 0, seen = fed;
+  for (const smx_cqt_config::Octave &o : c.octaves) {   // levels only grow down the plan
+    for (; level < c.early + o.halvings; ++level) seen = halved_ready(seen, lag);
+    least = std::min(least, cqt_octave_ready(c, o, seen));
+  }
+  return least;
+}
+
+// the most columns an octave holds that the slowest has not reached: octave i trails the input by less than the plan's
+// latency less D_i n_fft_i / 2 samples of it, and a column is `hop` of them
+int64_t cqt_run_ahead(const smx_cqt_config &c) {
+  const int64_t latency = c.latency();
+  int64_t worst = 0;
+  for (const smx_cqt_config::Octave &o : c.octaves) {
+    const int64_t d = int64_t(1) << (c.early + o.halvings);
+    worst = std::max(worst, ceil_div_pos(latency - d * (o.n_fft / 2), c.hop) + 1);
+  }
+  return worst;
+}
+
+// the most columns one step of at most max_block samples, or the flush, returns: a step moves the gate by its samples over the
+// hop, rounded up, and once more where the gate opens; the flush returns what the latency withheld
+int64_t cqt_column_bound(const smx_cqt_config &c, int64_t max_block) {
+  return std::max(ceil_div_pos(max_block, c.hop) + 1, ceil_div_pos(c.latency(), c.hop) + 1);
+}
+
+}  // namespace smx

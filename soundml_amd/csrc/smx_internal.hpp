@@ -300,6 +300,13 @@ smx_cqt_config *cqt_config_create(int64_t n_bins, int64_t sample_rate, double fm
                                   bool scale, int64_t hop, int pad, double pad_value);          // cqt_plan.cpp (cqt.ml:287-424)
 // the 0/1 fold [n_chroma; n_bins] of chroma.ml:332-366, its conditions raised under `op` (cqt_plan.cpp)
 std::vector<double> cqt_fold_matrix(const char *op, const smx_cqt_config &c, int64_t n_chroma);
+// the schedule of the streaming Cqt.Kernel in host integers (cqt_plan.cpp; cqt_stream.hip runs by it): the frames of an octave
+// complete within the first `seen` samples of its stream, the columns every octave has produced after `fed` input samples,
+// how many columns an octave can be ahead of the slowest, and the most columns one step of <= max_block samples or the flush returns
+int64_t cqt_octave_ready(const smx_cqt_config &c, const smx_cqt_config::Octave &o, int64_t seen);
+int64_t cqt_columns_ready(const smx_cqt_config &c, int64_t fed);
+int64_t cqt_run_ahead(const smx_cqt_config &c);
+int64_t cqt_column_bound(const smx_cqt_config &c, int64_t max_block);
 bool stft_nola(const smx_stft_config &c);                                        // stft.ml:731-743
 int64_t stft_output_length(const smx_stft_config &c, int64_t frames);            // stft.ml:792-796
 // envelope over the span of `frames` frames as three pieces: positions [0, head) and [stop, span) summed tap by

@@ -5,14 +5,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/soundml_amd.h"
 
 namespace smx {
 
-// sample s of the signal x[0, n) extended by `pad` (stft.ml:300-338), widened to double
-template <typename Tin>
-__device__ inline double fetch_sample(const Tin *x, int64_t n, int64_t s, int pad, double pad_value) {
+// sample s of the signal x[0, n) extended by `pad` (stft.ml:300-338), widened to double.  `x` is anything indexed by sample
+// position: a pointer, or a view of a signal that does not lie flat in memory (the history ring of cqt_stream.hip)
+template <typename Src>
+__device__ inline double fetch_sample_of(Src x, int64_t n, int64_t s, int pad, double pad_value) {
+  using Tin = std::decay_t<decltype(x[0])>;
   if (s >= 0 && s < n) return (double)x[s];
   if (pad == SMX_PAD_REFLECT) {  // stft.ml:300-305
     if (n == 1) return (double)x[0];
@@ -23,6 +26,11 @@ __device__ inline double fetch_sample(const Tin *x, int64_t n, int64_t s, int pa
   }
   if (pad == SMX_PAD_EDGE) return (double)x[s < 0 ? 0 : n - 1];
   return (double)(Tin)pad_value;   // the padded signal is built in the input dtype (stft.ml:318-338), then widened
+}
+
+template <typename Tin>
+__device__ inline double fetch_sample(const Tin *x, int64_t n, int64_t s, int pad, double pad_value) {
+  return fetch_sample_of(x, n, s, pad, pad_value);
 }
 
 // |z|^p with the reference's rounding order (stft.ml:670-674): the spectrum is

@@ -16,7 +16,14 @@ Each line is JSON.  ``power`` / ``chroma``: the library call.  ``chain``: the pl
 the library call that is decimation).  ``baseline``: the composition, in clip chunks of --baseline-chunk (its per-octave
 complex spectra do not fit otherwise), times summed.  ``flops`` counts 4 n_fft flops per (bin, frame) of the projection.
 --profile DIR runs ``rocprofv3 --kernel-trace --stats`` over a child process (three steps of ``power``) and prints the
-kernels' total and average times from its statistics."""
+kernels' total and average times from its statistics.
+
+--stream CHUNK times the streaming ``Cqt.Kernel`` instead: the same clips fed in chunks of CHUNK samples, HIP events around
+every ``step``.  ``stream``: the median and least time of a steady-state step (every octave is producing: the gate has opened),
+the total of all steps and the flush, and the library's kernel launches per steady-state step, its own three (append, project,
+emit) apart from the 2:1 stages'.  ``rerun``: what a user had before -- ``Cqt.transform`` of the last latency + CHUNK samples, for
+every chunk.  ``offline``: one ``Cqt.transform`` of the whole signal, next to the stream's total.  With --profile the child
+streams (one pass), and the statistics are per kernel over that pass."""
 import argparse
 import csv
 import glob
@@ -53,6 +60,8 @@ def profile(a):
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.profile, "--", sys.executable, os.path.abspath(__file__),
            "--plan", a.plan, "--rate", str(a.rate), "--clips", str(a.clips), "--seconds", str(a.seconds), "--steps", "3", "--warmup", "1",
            "--only", "power"]
+    if a.stream:
+        cmd += ["--stream", str(a.stream)]
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL)
     rows = []
     for path in glob.glob(os.path.join(a.profile, "**", "*kernel_stats.csv"), recursive=True):
@@ -63,6 +72,54 @@ def profile(a):
         print(json.dumps({"plan": a.plan, "rate": a.rate, "kernel": r["Name"][:120], "calls": int(r["Calls"]),
                           "total_ms": round(float(r["TotalDurationNs"]) * 1e-6, 3), "average_ms": round(float(r["AverageNs"]) * 1e-6, 4),
                           "share": round(float(r["TotalDurationNs"]) / total, 4)}))
+
+
+def stream(a, torch, Cqt, c, x, common):
+    from soundml_amd._lib import lib
+    n, chunk = x.shape[-1], a.stream
+    kern = Cqt.Kernel.prepare(c, channels=a.clips, max_block=chunk)
+    cuts = list(range(0, n, chunk)) + [n]
+    common = dict(common, chunk=chunk, latency=c.latency, chunks=len(cuts) - 1)
+
+    def one_pass():
+        kern.reset()
+        torch.cuda.synchronize()
+        events, launches = [], []
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            e0, e1, l0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), lib.smx_debug_kernel_launches()
+            e0.record()
+            out = kern.step(x[:, lo:hi])
+            e1.record()
+            events.append((lo, hi, e0, e1))
+            launches.append(lib.smx_debug_kernel_launches() - l0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        kern.flush()
+        e1.record()
+        torch.cuda.synchronize()
+        times = [(lo, hi, e0_.elapsed_time(e1_)) for lo, hi, e0_, e1_ in events]
+        return times, e0.elapsed_time(e1), launches
+
+    passes = 1 if a.only == "power" else max(1, a.warmup) + max(1, a.steps // 3)   # --only power: the profiled child
+    for k in range(passes):
+        times, flush_ms, launches = one_pass()
+    full = [lo >= c.latency + chunk and hi - lo == chunk for lo, hi, _ in times]   # the gate is open, and the chunk is whole
+    steady = sorted(t for (_, _, t), ok in zip(times, full) if ok)
+    steady_launches = [l for l, ok in zip(launches, full) if ok]
+    line = dict(common, case="stream", steady_steps=len(steady), flush_ms=round(flush_ms, 3),
+                total_ms=round(sum(t for _, _, t in times) + flush_ms, 3), decimator_stages=common["decimations"],
+                launches_per_steady_step=max(steady_launches) if steady_launches else None)
+    if steady:
+        line.update(ms_median=round(steady[len(steady) // 2], 4), ms_min=round(steady[0], 4))
+    print(json.dumps(line), flush=True)
+    if a.only == "power":
+        return
+    window = min(n, c.latency + chunk)
+    tail = x[:, n - window:]
+    med, least = timed(torch, lambda: Cqt.transform(c, tail), a.steps, a.warmup)
+    print(json.dumps(dict(common, case="rerun", window=window, ms_median=round(med, 4), ms_min=round(least, 4))), flush=True)
+    med, least = timed(torch, lambda: Cqt.transform(c, x), max(3, a.steps // 3), 1)
+    print(json.dumps(dict(common, case="offline", ms_median=round(med, 3), ms_min=round(least, 3))), flush=True)
 
 
 def main():
@@ -76,6 +133,7 @@ def main():
     ap.add_argument("--baseline-chunk", type=int, default=32)
     ap.add_argument("--only", default="")
     ap.add_argument("--profile", default="")
+    ap.add_argument("--stream", type=int, default=0, metavar="CHUNK")
     a = ap.parse_args()
     if a.profile:
         return profile(a)
@@ -99,6 +157,9 @@ def main():
 
     def report(case, med, least, **more):
         print(json.dumps(dict(common, case=case, ms_median=round(med, 3), ms_min=round(least, 3), **more)), flush=True)
+
+    if a.stream:
+        return stream(a, torch, Cqt, c, x, common)
 
     def chain():
         y = x
