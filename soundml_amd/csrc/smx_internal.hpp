@@ -45,11 +45,12 @@ void set_last_error(const std::string &message);
   } while (0)
 
 // ---- environment switches ------------------------------------------------------------------------------------------
-// The shipped library reads fourteen variables, each once per use and parsed ONE way (env_flag: unset -> -1, "0" / "" /
+// The shipped library reads fifteen variables, each once per use and parsed ONE way (env_flag: unset -> -1, "0" / "" /
 // "false" / "off" -> 0, anything else -> 1); none alters results except by selecting another kernel of the same contract:
 //   SMX_DISABLE_FAST   the generic kernels instead of the hand-laid ones (tests: two implementations of one contract)
 //   SMX_POWER_SKEW=0   fft-2048 / fft-1024 power spectrogram: the plain per-tile flush instead of whole aligned 64-byte blocks / 128-byte lines (tests, A/B timing)
 //   SMX_BORDER_INLINE=0 fft 2048 / 1024 / 512 (power / complex spectrogram, fused mel): the border frames in an epilogue / gathered strips instead of the tile sequence (tests: same values)
+//   SMX_P32_SHARE=0    fft-2048 power spectrogram: 32 sample requests per half-wave instead of the 20 that fetch a wave's two frames' span once (tests: bit-identical; A/B timing)
 //   SMX_COMPLEX_SKEW=0 fft-2048 Stft.transform: the plain per-tile flush instead of whole aligned 128-byte lines (tests, A/B timing)
 //   SMX_INVERT_PIPELINE=0 Stft.invert at fft 2048 / hop 512: the one-tile-per-workgroup kernel of rounds 1-4 instead of the persistent pipeline (tests, A/B timing)
 //   SMX_GL_FRAME_MAJOR=0 Griffin-Lim at fft 2048 / hop 512: its rebuilt spectra in the reference layout [bin][frame] instead of frame-major (tests: bit-identical; A/B timing)

@@ -258,6 +258,8 @@ template __global__ void stft2048_complex_fm_kernel<(SMX_ISA_ONE != 0)>(FastArgs
 template __global__ void stft_complex_lanes_kernel<SMX_ISA_ONE, true>(FastArgs);
 #elif SMX_ISA_KERNEL == 8
 template __global__ void stft4096_power64_kernel<true, 2, (SMX_ISA_ONE != 0)>(FastArgs);
+#elif SMX_ISA_KERNEL == 9
+template __global__ void stft2048_power32_kernel<true, 2, false, SMX_ISA_ONE, true>(FastArgs);
 #else
 template __global__ void stft2048_power32_kernel<true, 2, false, SMX_ISA_ONE>(FastArgs);
 #endif
@@ -534,6 +536,23 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
     const int skew_env = env_flag("SMX_POWER_SKEW");   // unset: a pair of frames per lane where the geometry is even, else a frame per lane; "0": the unskewed flush
     const int skew_form = (int)diag_int("SMX_POWER_SKEW_FORM", 0);   // diagnostic builds: 1 / 2 force a form
     const int skew = (strip || reinterpret_cast<uintptr_t>(a.out) % 4 != 0 || skew_env == 0) ? 0 : (skew_form == 2 || !even) ? 2 : 1;
+    // A wave fetches its two frames' span once (stft_fast_p32.hpp, SHARE): an even number of frames one hop of 512 apart (a wave has
+    // both of its frames or none) from 8-byte aligned samples, no strips; where border tiles ride in the sequence their waves' unused
+    // request reads the clip's first fft + hop samples.  SMX_P32_SHARE=0: the requests per half-wave (same values: tested).
+    const bool share = aligned && !strip && c.hop == 512 && count % 2 == 0 && a.fold_frames != 1 && (a.fold_frames != 2 || n >= kN + 512) &&
+                       env_flag("SMX_P32_SHARE") != 0;
+    if (share) {
+      if (skew) a.interleave = 0;
+      auto by_power = [&](auto sk) {
+        constexpr int K = decltype(sk)::value;
+        return a.pmode == 2 ? stft2048_power32_kernel<true, 2, false, K, true> : a.pmode == 1 ? stft2048_power32_kernel<true, 1, false, K, true> : stft2048_power32_kernel<true, 0, false, K, true>;
+      };
+      auto k32p = skew == 1 ? by_power(std::integral_constant<int, 1>{}) : skew == 2 ? by_power(std::integral_constant<int, 2>{}) : by_power(std::integral_constant<int, 0>{});
+      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k32p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
+      SMX_LAUNCH(k32p, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a);
+      SMX_HIP_CHECK(hipGetLastError());
+      return;
+    }
     if (skew) {
       a.interleave = 0;
       auto by_power = [&](auto al, auto sk) {

@@ -335,6 +335,8 @@ struct NoMid32 {
 // frame waves must fit 168 registers.
 // CPLX: 0 |X|^p into the tile; 1 the spectrum into the tile's two planes; 2 the spectrum handed to mid.emit() / mid.emit_self() slot
 // by slot (Griffin-Lim's frame-major spectra: nothing of a frame stays in LDS, so waves never meet)
+template <class Mid, class = void> struct mid_unpacks32 : std::false_type {};
+template <class Mid> struct mid_unpacks32<Mid, std::enable_if_t<Mid::kSharedSpan>> : std::true_type {};
 template <int PMODE, class Mid, int CPLX = 0, int TWFIRST = 15>
 __device__ __forceinline__ void frame32_to_tile(const FastArgs &a, const Lane32 &L, float2 (&raw)[32], float *tile,
                                                 const Mid &mid) {
@@ -349,6 +351,9 @@ __device__ __forceinline__ void frame32_to_tile(const FastArgs &a, const Lane32 
   float4 winE[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) winE[m] = L.win_l()[32 * m];
+  if constexpr (mid_unpacks32<Mid>::value) {   // the power kernel's shared span: the two halves' samples dealt out under the window's round trip (load_pair32_shared)
+    SMX_FENCE(); mid.unpack(); SMX_FENCE();
+  }
 #pragma unroll
   for (int m = 0; m < 8; ++m) {   // even points j = 4 m, 4 m + 2 -> e[2 m], e[2 m + 1]
     e[2 * m] = f2{raw[4 * m].x, raw[4 * m].y} * f2{winE[m].x, winE[m].y};
@@ -621,6 +626,41 @@ __device__ __forceinline__ void load_frame32(const float *src, int l, float2 (&r
       const int e = 64 * (j & 15);
       raw[j] = make_float2(b[e], b[e + 1]);
     }
+  }
+}
+
+// SHARE (the power kernel, round 10): the two halves of a wave hold frames ONE hop of 512 samples apart, so together they span 2560
+// samples = 40 pieces of 256 bytes, of which load_frame32 asks for 64 (32 requests, each `piece j | piece j + 8`).  Here the span is
+// fetched once: 20 requests S[m] whose 64 lanes read the 512 contiguous bytes from 512 m on -- lanes 0-31 piece 2 m, lanes 32-63
+// piece 2 m + 1 -- and unpack_pair32, behind the frame's wait, deals them out: v_permlane32_swap on (S[m], S[m + 4]) turns
+// (2m | 2m+1), (2m+8 | 2m+9) into (2m | 2m+8), (2m+1 | 2m+9) = raw[2 m], raw[2 m + 1]: the same sample in the same register of the
+// same lane as load_frame32 leaves there.  S[4..15] serve two pairings each and are copied first (24 v_mov_b32).  In place: S[m]
+// waits in raw[2 m] (m < 16) and S[16..19] in raw[25], raw[27], raw[29], raw[31] -- where their swaps leave raw[2 m + 1].
+// `span` (wave-uniform, 8-byte aligned) is the first sample of the lower half's frame; the 40 pieces end with the upper half's
+// frame, so nothing past a frame of the request is read.
+// (Measured, profiles/r10/NOTES.md: C2 0.4610 -> 0.4435 ms interleaved, A/A spread 0.0004.  Odd waves starting at S[8], so that an
+// odd wave and its successor ask for the same 512 bytes at 12 of the 20 steps -- r09's order carried over -- bought another 0.0026
+// in a log whose A/A spread was 0.0014: inside the margin of three spreads, not kept.)
+constexpr int pair32_slot(int m) { return m < 16 ? 2 * m : 2 * m - 7; }
+__device__ __forceinline__ void load_pair32_shared(const float *span /* wave-uniform */, int lane, float2 (&raw)[32]) {
+  long off8 = 512, off16 = 1024;
+  asm volatile("" : "+s"(off8), "+s"(off16));   // two more scalar bases (13-bit immediates reach 8 x 512 bytes), one lane offset
+  const float2 *s0 = reinterpret_cast<const float2 *>(span);
+  const float2 *p0 = s0 + lane, *p8 = (s0 + off8) + lane, *p16 = (s0 + off16) + lane;
+#pragma unroll
+  for (int m = 0; m < 20; ++m) raw[pair32_slot(m)] = (m < 8 ? p0 : m < 16 ? p8 : p16)[64 * (m & 7)];
+}
+__device__ __forceinline__ void swap_halves32(float &a, float &b) {   // a = (a.lo | b.lo), b = (a.hi | b.hi)
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void unpack_pair32(float2 (&raw)[32]) {
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    if (m < 12) raw[2 * m + 1] = raw[pair32_slot(m + 4)];   // (S[m + 4] is paired again at step m + 4)
+    swap_halves32(raw[2 * m].x, raw[2 * m + 1].x);
+    swap_halves32(raw[2 * m].y, raw[2 * m + 1].y);
   }
 }
 
@@ -923,8 +963,9 @@ __device__ __forceinline__ void skewg32_store(const FastArgs &a, const SkewG32 &
 }
 
 // what the power kernel does between the stages of a frame pair (see frame32_to_tile)
-template <bool ALIGNED, int SKEW = 0>
+template <bool ALIGNED, int SKEW = 0, bool SHARE = false>
 struct PowerMid32 {
+  static constexpr bool kSharedSpan = SHARE;
   const FastArgs &a;
   const Lds32 &lds;
   const Flush32 &fl;
@@ -940,6 +981,8 @@ struct PowerMid32 {
   const float *src;      // the next frames' samples (per lane)
   const float *src_clip; // ... their clip (wave-uniform) and whether their tile holds a frame that reaches past the signal
   bool src_border;
+  const float *span;     // SHARE: the first sample of the next frame PAIR (wave-uniform) ...
+  bool packed;           // ... and whether this frame's samples wait as that pair's span (a border tile's do not)
   float *pend_out;       // output origin and frames of the previous tile
   int pend_left;
   int lane, wave, b, it;
@@ -948,11 +991,22 @@ struct PowerMid32 {
   // for border tiles, or the padding rule there, made the loop spill (9 to 37 registers; the compiler's allocation, not a
   // count of live values): this form costs one register.  The two border tiles of a clip begin a memory round trip late.
   __device__ __forceinline__ void load_next() const {
-    const float *from = src_border ? src_clip : src;
+    if constexpr (SHARE) {   // (a border tile: the clip's first 2560 samples -- the launcher admits n >= fft + hop)
+      const float *from = src_border ? src_clip : span;
 #ifdef SMX_DIAG
-    if (a.abl_p32 & 1) from = src;   // (src_clip is clip 0 and src its resident frame: a border tile asks for that frame on both paths)
+      if (a.abl_p32 & 1) from = span;   // (the resident pair, as below)
 #endif
-    load_frame32<ALIGNED, true>(from, lane & 31, raw, (wave & 1) != 0);
+      load_pair32_shared(from, lane, raw);
+    } else {
+      const float *from = src_border ? src_clip : src;
+#ifdef SMX_DIAG
+      if (a.abl_p32 & 1) from = src;   // (src_clip is clip 0 and src its resident frame: a border tile asks for that frame on both paths)
+#endif
+      load_frame32<ALIGNED, true>(from, lane & 31, raw, (wave & 1) != 0);
+    }
+  }
+  __device__ __forceinline__ void unpack() const {
+    if (packed) unpack_pair32(raw);   // (wave-uniform)
   }
   __device__ __forceinline__ void load_next_border() const {
     if (src_border) load_frame32_padded(a, src_clip, (int)(src - src_clip), lane & 31, raw);
@@ -1019,8 +1073,13 @@ struct PowerMid32 {
   }
 };
 
-template <bool ALIGNED, int PMODE, bool STRIP, int SKEW = 0>
+// SHARE: a wave fetches its two frames' span once (load_pair32_shared) -- the kernel's only request path besides the padding
+// rule, in instantiations of its own: the launcher takes them for requests of an EVEN number of frames one hop of 512 apart from
+// 8-byte aligned samples (a wave then has both of its frames or none), without strips, and with n >= fft + hop where border tiles
+// ride in the sequence.
+template <bool ALIGNED, int PMODE, bool STRIP, int SKEW = 0, bool SHARE = false>
 __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
+  static_assert(!SHARE || (ALIGNED && !STRIP), "the shared span needs aligned samples and no strips");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1056,6 +1115,14 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
     }
     return xc + (p * a.hop - a.left);   // (fold_frames == 2: possibly outside the clip -- then only its position is used)
   };
+  // SHARE: first sample of this wave's frame pair in tile t (wave-uniform; a wave without frames takes the tile's first two,
+  // which exist: the count is even)
+  auto span_ptr = [&](const float *xc, int t) {
+    const int64_t f0 = (int64_t)t * kFT;
+    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
+    const int fi = 2 * wave;
+    return xc + ((a.p0 + f0 + (fi <= avail ? fi : 0)) * a.hop - a.left);
+  };
   // fold_frames == 2: one of THIS WAVE's two frames of tile t reaches past the signal: the wave takes load_frame32_padded for
   // the tile (wave-uniform; the other waves of such a tile keep the plain requests -- a C2 clip's first tile has its border
   // frames on wave 0, its last one on wave 4: with the whole tile on the padding rule the prologue's requests alone took
@@ -1068,7 +1135,7 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
       const int fi = 2 * wave + hh;
-      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
+      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : (SHARE ? hh : 0));   // (SHARE: a wave without frames reads the tile's frames 0 AND 1)
       any = any || p < a.border_i0 || p >= a.border_i1;
     }
     return any;
@@ -1077,11 +1144,13 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);
+  bool raw_packed = false;   // SHARE (wave-uniform): `raw` holds a frame pair's span as requested, not yet dealt out to the halves
   // the first frames' samples are requested BEFORE the tables are filled: both round trips overlap (round 5: the prologue was
   // 5.8 us of a 0.49 ms C2 launch, profiles/r07/timeline_before.log)
   if (ntiles > 0) {
     const float *src0 = frame_ptr(tw.xclip, tw.ft);
     if (tile_border(tw.ft)) load_frame32_padded(a, tw.xclip, (int)(src0 - tw.xclip), L.l, raw);
+    else if constexpr (SHARE) { load_pair32_shared(span_ptr(tw.xclip, tw.ft), lane, raw); raw_packed = true; }
     else load_frame32<ALIGNED>(src0, L.l, raw);
   }
 #ifdef SMX_STAMPS
@@ -1144,6 +1213,13 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
     // tile keeps both of its request paths, each on that frame: load_frame32_padded takes its position from src - src_clip.
     if (a.abl_p32 & 1) { src_clip = a.x; src = frame_ptr(a.x, 1); }
 #endif
+    const float *span = nullptr;
+    if constexpr (SHARE) {
+      span = span_ptr(src_clip, more ? ftnext : tw.ft);
+#ifdef SMX_DIAG
+      if (a.abl_p32 & 1) span = span_ptr(a.x, 1);
+#endif
+    }
     const bool have = (int64_t)tw.ft * kFT + 2 * wave < a.count;   // wave-uniform: at least the first half has a frame
     if constexpr (SKEW == 1) {
       if (it > 0 && pend_fresh) skew32_clip(a, sk, pend_oclip, lane, wave);   // (wave-uniform) the pending tile begins a clip or this workgroup's range
@@ -1151,9 +1227,9 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
       if (it > 0 && pend_fresh) skewg32_clip(a, skg, pend_oclip, lane, wave);
     }
 #ifdef SMX_STAMPS
-    const PowerMid32<ALIGNED, SKEW> mid{a, lds, fl, fr, sk, sr, carry, skg, srg, carryg, pend_fresh, pend_closing, raw, src, src_clip, src_border, pend_out, pend_left, lane, wave, b, it, stamp_sum, &stamp_prev, pk_drained, pk_filled};
+    const PowerMid32<ALIGNED, SKEW, SHARE> mid{a, lds, fl, fr, sk, sr, carry, skg, srg, carryg, pend_fresh, pend_closing, raw, src, src_clip, src_border, span, raw_packed, pend_out, pend_left, lane, wave, b, it, stamp_sum, &stamp_prev, pk_drained, pk_filled};
 #else
-    const PowerMid32<ALIGNED, SKEW> mid{a, lds, fl, fr, sk, sr, carry, skg, srg, carryg, pend_fresh, pend_closing, raw, src, src_clip, src_border, pend_out, pend_left, lane, wave, b, it, pk_drained, pk_filled};
+    const PowerMid32<ALIGNED, SKEW, SHARE> mid{a, lds, fl, fr, sk, sr, carry, skg, srg, carryg, pend_fresh, pend_closing, raw, src, src_clip, src_border, span, raw_packed, pend_out, pend_left, lane, wave, b, it, pk_drained, pk_filled};
 #endif
     mid.template stamp<0>();
 #ifdef SMX_STAMPS
@@ -1187,6 +1263,7 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
     pend_oclip = tw.oclip;
     pend_fresh = it == 0 || tw.ft == 0;
     pend_closing = tw.ft == a.tiles_per_clip - 1;
+    if constexpr (SHARE) raw_packed = !src_border;
     tw.xclip = xnext;
     tw.oclip = onext;
     tw.ft = ftnext;

@@ -8,6 +8,9 @@ compare separate runs or boxes (boxes differ by +-10 % on one binary: the board'
   VARIANT = "[path/to/libsoundml_amd.so][@VAR=value[,VAR=value...]]"     "" = the shipped build, default environment
             e.g.  ""  "@SMX_POWER_SKEW=0"  "soundml_amd/lib_x/libsoundml_amd.so"  "soundml_amd/lib_diag/libsoundml_amd.so@SMX_NOSTORE=1"
             (options the library reads per launch; a switch read once per process needs a process of its own)
+            An A/A pair: the same library twice under two names, e.g.  "x.so"  "x.so@SMX_AA=1"  (a variable nobody reads).
+            The sample fetch of the fft-2048 power kernel (profiles/r10):  ""  "@SMX_P32_SHARE=0"  = the frame pair's span fetched once /
+            the 32 requests per half-wave, in one build.
 
 Prints a checksum per variant and whether its output equals the first variant's bit for bit, then min / quartiles of the
 interleaved rounds (HIP events around 4 launches).  --energy: afterwards every variant runs back to back for ~2.5 s while rocm-smi
