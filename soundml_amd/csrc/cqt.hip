@@ -163,28 +163,17 @@ void cqt_host(const smx_cqt_config *c, const char *op, const float *x, int64_t l
   const int64_t count = c->frames(n);
   if (lead == 0 || count == 0) return;
   if (!x || !out) throw Failure(format("%s: null pointer", op));
-  require_device();
-  const size_t in_bytes = (size_t)lead * (size_t)n * sizeof(float);
-  const size_t out_bytes = (size_t)lead * (size_t)c->n_bins * (size_t)count * (mode == OUT_COMPLEX ? 8 : 4);
-  DeviceScratch d_x(in_bytes), d_out(out_bytes);
-  copy_to_device(d_x.ptr, x, in_bytes);
-  cqt_dev(*c, op, d_x.as<float>(), lead, n, n, mode, power, d_out.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, d_out.ptr, out_bytes);
+  host_call(op, {{x, (size_t)n * sizeof(float)}}, out, (size_t)c->n_bins * (size_t)count * (mode == OUT_COMPLEX ? 8 : 4), lead, false, nullptr,
+            [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              cqt_dev(*c, op, reinterpret_cast<const float *>(d_in[0]), nc, n, n, mode, power, d_out, stream);
+            });
 }
 
 // ---- Chroma.of_cqt / Soundml.chroma_cqt --------------------------------------------------------------------------------
-void check_norm(const char *op, int norm, double norm_p) {   // chroma.ml:31-40
-  if (norm == SMX_CHROMA_NORM_NONE || norm == SMX_CHROMA_NORM_INF) return;
-  if (norm != SMX_CHROMA_NORM_P) throw Failure(format("%s: unknown norm %d", op, norm));
-  if (!(std::isfinite(norm_p) && norm_p > 0.0))
-    throw InvalidArgument(format("%s: cannot normalise in the %g-norm (the exponent must be finite and positive)", op, norm_p));
-}
-
 // the conditions of chroma.ml:371-381 in the reference's order; true when there is something to compute
 bool check_of_cqt(const smx_cqt_config *c, int64_t lead, int64_t bins, int64_t frames, int64_t n_chroma, int norm, double norm_p) {
   if (!c) throw Failure("of_cqt: configuration handle is null");
-  check_norm("of_cqt", norm, norm_p);
+  check_chroma_norm("of_cqt", norm, norm_p);
   (void)cqt_fold_matrix("of_cqt", *c, n_chroma);
   if (lead < 0 || bins < 0 || frames < 0) throw Failure("of_cqt: negative extent");
   if (bins != c->n_bins)
@@ -216,21 +205,18 @@ void of_cqt_host(const smx_cqt_config *c, const void *s, int elem_bytes, int64_t
                  int norm, double norm_p, void *out) {
   if (!check_of_cqt(c, lead, bins, frames, n_chroma, norm, norm_p)) return;
   if (!s || !out) throw Failure("of_cqt: null pointer");
-  require_device();
-  const size_t in_bytes = (size_t)lead * (size_t)bins * (size_t)frames * (size_t)elem_bytes;
-  const size_t out_bytes = (size_t)lead * (size_t)n_chroma * (size_t)frames * (size_t)elem_bytes;
-  DeviceScratch d_s(in_bytes), d_out(out_bytes);
-  copy_to_device(d_s.ptr, s, in_bytes);
-  of_cqt_dev(*c, d_s.ptr, elem_bytes, lead, bins, frames, n_chroma, norm, norm_p, d_out.ptr, nullptr);
-  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  copy_to_host(out, d_out.ptr, out_bytes);
+  const size_t row = (size_t)frames * (size_t)elem_bytes;
+  host_call("of_cqt", {{s, (size_t)bins * row}}, out, (size_t)n_chroma * row, lead, false, nullptr,
+            [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              of_cqt_dev(*c, d_in[0], elem_bytes, nc, bins, frames, n_chroma, norm, norm_p, d_out, stream);
+            });
 }
 
 // of_cqt of power_spectrum ~power:1; the magnitudes live in scratch on the device
 void chroma_cqt_dev(const smx_cqt_config &c, const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t n_chroma, int norm,
                     double norm_p, float *d_out, hipStream_t stream) {
   check_cqt(&c, "chroma_cqt", lead, n);
-  check_norm("of_cqt", norm, norm_p);
+  check_chroma_norm("of_cqt", norm, norm_p);
   (void)cqt_fold_matrix("of_cqt", c, n_chroma);
   const int64_t count = c.frames(n);
   if (lead == 0 || count == 0) return;
@@ -443,18 +429,16 @@ int smx_chroma_cqt_f32(const smx_cqt_config *c, const float *x, int64_t lead, in
                        float *out) {
   return guarded([&] {
     check_cqt(c, "chroma_cqt", lead, n);
-    check_norm("of_cqt", norm, norm_p);
+    check_chroma_norm("of_cqt", norm, norm_p);
     (void)cqt_fold_matrix("of_cqt", *c, n_chroma);
     const int64_t count = c->frames(n);
     if (lead == 0 || count == 0) return;
     if (!x || !out) throw Failure("chroma_cqt: null pointer");
-    require_device();
-    const size_t in_bytes = (size_t)lead * (size_t)n * sizeof(float), out_bytes = (size_t)lead * (size_t)n_chroma * (size_t)count * sizeof(float);
-    DeviceScratch d_x(in_bytes), d_out(out_bytes);
-    copy_to_device(d_x.ptr, x, in_bytes);
-    chroma_cqt_dev(*c, d_x.as<float>(), lead, n, n, n_chroma, norm, norm_p, d_out.as<float>(), nullptr);
-    SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    copy_to_host(out, d_out.ptr, out_bytes);
+    host_call("chroma_cqt", {{x, (size_t)n * sizeof(float)}}, out, (size_t)n_chroma * (size_t)count * sizeof(float), lead, false, nullptr,
+              [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+                chroma_cqt_dev(*c, reinterpret_cast<const float *>(d_in[0]), nc, n, n, n_chroma, norm, norm_p,
+                               reinterpret_cast<float *>(d_out), stream);
+              });
   });
 }
 int smx_chroma_cqt_f32_dev(const smx_cqt_config *c, const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t n_chroma,

@@ -441,6 +441,7 @@ int smx_cqt_kernel_flush_f32_dev(smx_cqt_kernel *k, void *d_out, int64_t out_str
   });
 }
 
+// the host forms of step and flush are not batch calls (strided rows, a column count known only after the run): no host_call
 int smx_cqt_kernel_step_f32(smx_cqt_kernel *k, const float *x, int64_t n, int64_t x_stride, void *out, int64_t out_stride, int64_t *columns) {
   return guarded([&] {
     kernel_check(k, "step");

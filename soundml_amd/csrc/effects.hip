@@ -254,3 +254,251 @@ void launch_pvoc(const PvocJob &job) {
 }
 
 }  // namespace smx
+
+// ---- the C ABI's side: Effects ---------------------------------------------------------------------------------------------
+namespace smx {
+namespace {
+
+// ---- Effects (effects.ml:96-123, 285-334): checks in the reference's order and words, then the launches ---------------------
+bool pvoc_locked(const char *fn, int phase) {
+  if (phase != SMX_PHASE_INDEPENDENT && phase != SMX_PHASE_LOCKED) throw Failure(format("%s: unknown phase mode %d", fn, phase));
+  return phase == SMX_PHASE_LOCKED;
+}
+
+// check_rate, check_spectrum (effects.ml:96-117; the rank is what the entry point's signature states); the output frame count
+int64_t check_vocoder(const smx_stft_config *c, double rate, int phase, int64_t lead, int64_t bins, int64_t frames) {
+  check_stretch_rate("phase_vocoder", rate);
+  check_config(c, "phase_vocoder");
+  if (lead < 0 || bins < 0 || frames < 0)
+    throw Failure(format("phase_vocoder: negative extent (lead %lld, bins %lld, frames %lld)", (long long)lead, (long long)bins,
+                         (long long)frames));
+  if (bins != c->bins())
+    throw InvalidArgument(format("phase_vocoder: cannot vocode %lld frequency bins of a %lld-point transform (the bin axis must hold "
+                                 "fft_size / 2 + 1 = %lld values)", (long long)bins, (long long)c->fft_size, (long long)c->bins()));
+  pvoc_locked("phase_vocoder", phase);
+  return pvoc_out_frames(frames, rate);
+}
+
+void vocoder_dev(const smx_stft_config &c, const void *d_z, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, double rate,
+                 int phase, void *d_out, hipStream_t stream) {
+  const int64_t count = check_vocoder(&c, rate, phase, lead, bins, frames);
+  if (lead == 0 || count == 0) return;   // a spectrum with no frames is a spectrum with no frames
+  if (!d_z || !d_out) throw Failure("phase_vocoder: null device pointer");
+  PvocJob job;
+  job.z = d_z;
+  job.elem_bytes = elem_bytes;
+  job.lead = lead;
+  job.bins = bins;
+  job.frames = frames;
+  job.count = count;
+  job.fft_size = c.fft_size;
+  job.hop = c.hop;
+  job.rate = rate;
+  job.locked = phase == SMX_PHASE_LOCKED;
+  job.out = d_out;
+  job.stream = stream;
+  launch_pvoc(job);
+}
+
+void vocoder_host(const smx_stft_config *c, const void *z, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, double rate,
+                  int phase, void *out) {
+  const int64_t count = check_vocoder(c, rate, phase, lead, bins, frames);
+  if (lead == 0 || count == 0) return;
+  if (!z || !out) throw Failure("phase_vocoder: null pointer");
+  const size_t cell = 2 * (size_t)elem_bytes;
+  host_call("phase_vocoder", {{z, (size_t)bins * (size_t)frames * cell}}, out, (size_t)bins * (size_t)count * cell, lead, false, nullptr,
+            [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              vocoder_dev(*c, d_in[0], elem_bytes, nc, bins, frames, rate, phase, d_out, stream);
+            });
+}
+
+// `time_stretch` (effects.ml:291-298): rate, rank (the signature's), then what Stft.invert checks for the length it will be asked for
+struct StretchPlan {
+  int64_t frames = 0, count = 0, length = 0;
+};
+StretchPlan check_stretch(const smx_stft_config *c, double rate, int phase, int64_t lead, int64_t n) {
+  check_stretch_rate("time_stretch", rate);
+  check_config(c, "time_stretch");
+  check_rank_extents("time_stretch", lead, n);
+  pvoc_locked("time_stretch", phase);
+  StretchPlan p;
+  p.length = stretch_length(n, rate);
+  check_synthesis("invert", *c, c->bins(), p.length, true);
+  p.frames = c->frames(n);
+  p.count = pvoc_out_frames(p.frames, rate);
+  return p;
+}
+
+// Stft.transform -> vocoder -> Stft.invert ~length inside the library, bit for bit those three calls.  The two complex stacks live
+// in scratch and the batch goes through in clip chunks that keep them bounded (every clip is stretched on its own).  float64 audio,
+// and float32 audio under the float64 interior (widened first, the result rounded once: effects.ml:291-298), keep complex128
+// spectra between the stages.
+void stretch_dev(const smx_stft_config &c, const void *d_x, int in_bytes, int64_t lead, int64_t n, double rate, int phase, void *d_y,
+                 hipStream_t stream) {
+  const StretchPlan p = check_stretch(&c, rate, phase, lead, n);
+  if (lead == 0 || p.length == 0) return;
+  if (!d_y || (n > 0 && !d_x)) throw Failure("time_stretch: null device pointer");
+  if (p.count == 0) {   // no analysis frame: silence
+    SMX_HIP_CHECK(hipMemsetAsync(d_y, 0, (size_t)lead * (size_t)p.length * (size_t)in_bytes, stream));
+    return;
+  }
+  const int work = in_bytes == 8 || interior() == SMX_INTERIOR_F64 ? 8 : 4;
+  const bool widen = work != in_bytes;
+  const int64_t bins = c.bins();
+  const size_t cell = 2 * (size_t)work;
+  const size_t plane = (size_t)bins * (size_t)std::max(p.frames, p.count) * cell;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(lead, (int64_t)(((size_t)256 << 20) / std::max<size_t>(plane, 1))));
+  init_device_pool();
+  DeviceScratch z, stretched, wide_x, wide_y;
+  z.pool(std::max<size_t>(16, (size_t)chunk * (size_t)bins * (size_t)p.frames * cell), stream);
+  stretched.pool(std::max<size_t>(16, (size_t)chunk * (size_t)bins * (size_t)p.count * cell), stream);
+  if (widen) {
+    wide_x.pool(std::max<size_t>(16, (size_t)chunk * (size_t)n * 8), stream);
+    wide_y.pool(std::max<size_t>(16, (size_t)chunk * (size_t)p.length * 8), stream);
+  }
+  for (int64_t c0 = 0; c0 < lead; c0 += chunk) {
+    const int64_t nc = std::min(chunk, lead - c0);
+    const void *src = reinterpret_cast<const unsigned char *>(d_x) + (size_t)c0 * (size_t)n * (size_t)in_bytes;
+    void *dst = reinterpret_cast<unsigned char *>(d_y) + (size_t)c0 * (size_t)p.length * (size_t)in_bytes;
+    if (widen) {
+      launch_gl_widen(reinterpret_cast<const float *>(src), wide_x.as<double>(), nc * n, stream);
+      src = wide_x.ptr;
+    }
+    stft_range_dev(c, src, work, nc, n, n, 0, p.frames, OUT_COMPLEX, 2.0, z.ptr, stream);
+    vocoder_dev(c, z.ptr, work, nc, bins, p.frames, rate, phase, stretched.ptr, stream);
+    invert_dev(c, stretched.ptr, 2 * work, nc, bins, p.count, 1, p.length, widen ? wide_y.ptr : dst, stream);
+    if (widen) launch_gl_narrow(wide_y.as<double>(), reinterpret_cast<float *>(dst), nc * p.length, stream);
+  }
+}
+
+void stretch_host(const smx_stft_config *c, const void *x, int in_bytes, int64_t lead, int64_t n, double rate, int phase, void *y) {
+  const StretchPlan p = check_stretch(c, rate, phase, lead, n);
+  if (lead == 0 || p.length == 0) return;
+  if (!y || (n > 0 && !x)) throw Failure("time_stretch: null pointer");
+  host_call("time_stretch", {{x, (size_t)n * (size_t)in_bytes}}, y, (size_t)p.length * (size_t)in_bytes, lead, false, nullptr,
+            [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) { stretch_dev(*c, d_in[0], in_bytes, nc, n, rate, phase, d_out, stream); });
+}
+
+// `pitch_shift` (effects.ml:324-334): time_stretch at den / num (this very quotient: the vocoder is chaotic in its rate), the
+// resampler built for num -> den, then the cut or zero-extension to n; the stretched signal stays on the device between the
+// stages.  DEVIATION: Resample.apply is float32 here, so float64 audio is stretched in float64 and converted in float32.
+struct ShiftPlan {
+  double rate = 1.0;
+  StretchPlan stretch;
+  int64_t resampled = 0;
+};
+ShiftPlan check_shift(const smx_stft_config *c, const smx_resample_config *r, int phase, int64_t lead, int64_t n) {
+  check_config(c, "pitch_shift");
+  check_config(r, "pitch_shift");
+  check_rank_extents("pitch_shift", lead, n);
+  ShiftPlan p;
+  p.rate = (double)smx_resample_config_target(r) / (double)smx_resample_config_sample_rate(r);
+  p.stretch = check_stretch(c, p.rate, phase, lead, n);
+  if (smx_resample_config_output_frames(r, p.stretch.length, &p.resampled) != SMX_OK) throw InvalidArgument(smx_last_error());
+  return p;
+}
+
+void shift_dev(const smx_stft_config &c, const smx_resample_config &r, int phase, const void *d_x, int in_bytes, int64_t lead, int64_t n,
+               void *d_y, hipStream_t stream) {
+  const ShiftPlan p = check_shift(&c, &r, phase, lead, n);
+  if (lead == 0 || n == 0) return;
+  if (!d_x || !d_y) throw Failure("pitch_shift: null device pointer");
+  const int64_t length = p.stretch.length, kept = std::min(n, p.resampled);
+  init_device_pool();
+  DeviceScratch stretched, resampled, wide, fixed;
+  stretched.pool(std::max<size_t>(16, (size_t)lead * (size_t)length * 4), stream);
+  resampled.pool(std::max<size_t>(16, (size_t)lead * (size_t)p.resampled * 4), stream);
+  if (in_bytes == 8) {
+    wide.pool(std::max<size_t>(16, (size_t)lead * (size_t)length * 8), stream);
+    fixed.pool((size_t)lead * (size_t)n * 4, stream);
+    stretch_dev(c, d_x, 8, lead, n, p.rate, phase, wide.ptr, stream);
+    if (length > 0) launch_gl_narrow(wide.as<double>(), stretched.as<float>(), lead * length, stream);
+  } else {
+    stretch_dev(c, d_x, 4, lead, n, p.rate, phase, stretched.ptr, stream);
+  }
+  if (p.resampled > 0) {
+    const int code = smx_resample_apply_f32_dev(&r, stretched.as<float>(), lead, length, length, resampled.as<float>(), p.resampled, stream);
+    if (code != SMX_OK) {
+      if (code == SMX_INVALID_ARGUMENT) throw InvalidArgument(smx_last_error());
+      throw Failure(smx_last_error());
+    }
+  }
+  float *out = in_bytes == 8 ? fixed.as<float>() : reinterpret_cast<float *>(d_y);   // fix_length, effects.ml:302-314
+  if (kept < n) SMX_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)lead * (size_t)n * 4, stream));
+  if (kept > 0)
+    SMX_HIP_CHECK(hipMemcpy2DAsync(out, (size_t)n * 4, resampled.ptr, (size_t)p.resampled * 4, (size_t)kept * 4, (size_t)lead,
+                                   hipMemcpyDeviceToDevice, stream));
+  if (in_bytes == 8) launch_gl_widen(fixed.as<float>(), reinterpret_cast<double *>(d_y), lead * n, stream);
+}
+
+void shift_host(const smx_stft_config *c, const smx_resample_config *r, int phase, const void *x, int in_bytes, int64_t lead, int64_t n,
+                void *y) {
+  check_shift(c, r, phase, lead, n);
+  if (lead == 0 || n == 0) return;
+  if (!x || !y) throw Failure("pitch_shift: null pointer");
+  const size_t row = (size_t)n * (size_t)in_bytes;
+  host_call("pitch_shift", {{x, row}}, y, row, lead, false, nullptr, [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+    shift_dev(*c, *r, phase, d_in[0], in_bytes, nc, n, d_out, stream);
+  });
+}
+
+}  // namespace
+}  // namespace smx
+
+using namespace smx;
+
+extern "C" {
+
+// ---- Effects (effects.ml) ---------------------------------------------------------------------------
+int smx_phase_vocoder_c64(const smx_stft_config *c, const float *z, int64_t lead, int64_t bins, int64_t frames, double rate, int phase,
+                          float *out) {
+  return guarded([&] { vocoder_host(c, z, 4, lead, bins, frames, rate, phase, out); });
+}
+int smx_phase_vocoder_c128(const smx_stft_config *c, const double *z, int64_t lead, int64_t bins, int64_t frames, double rate, int phase,
+                           double *out) {
+  return guarded([&] { vocoder_host(c, z, 8, lead, bins, frames, rate, phase, out); });
+}
+int smx_phase_vocoder_c64_dev(const smx_stft_config *c, const float *d_z, int64_t lead, int64_t bins, int64_t frames, double rate,
+                              int phase, float *d_out, void *stream) {
+  return guarded([&] {
+    check_vocoder(c, rate, phase, lead, bins, frames);
+    vocoder_dev(*c, d_z, 4, lead, bins, frames, rate, phase, d_out, (hipStream_t)stream);
+  });
+}
+int smx_phase_vocoder_c128_dev(const smx_stft_config *c, const double *d_z, int64_t lead, int64_t bins, int64_t frames, double rate,
+                               int phase, double *d_out, void *stream) {
+  return guarded([&] {
+    check_vocoder(c, rate, phase, lead, bins, frames);
+    vocoder_dev(*c, d_z, 8, lead, bins, frames, rate, phase, d_out, (hipStream_t)stream);
+  });
+}
+int smx_time_stretch_f32(const smx_stft_config *c, const float *x, int64_t lead, int64_t n, double rate, int phase, float *y) {
+  return guarded([&] { stretch_host(c, x, 4, lead, n, rate, phase, y); });
+}
+int smx_time_stretch_f64(const smx_stft_config *c, const double *x, int64_t lead, int64_t n, double rate, int phase, double *y) {
+  return guarded([&] { stretch_host(c, x, 8, lead, n, rate, phase, y); });
+}
+int smx_time_stretch_f32_dev(const smx_stft_config *c, const float *d_x, int64_t lead, int64_t n, double rate, int phase, float *d_y,
+                             void *stream) {
+  return guarded([&] {
+    check_stretch(c, rate, phase, lead, n);
+    stretch_dev(*c, d_x, 4, lead, n, rate, phase, d_y, (hipStream_t)stream);
+  });
+}
+int smx_pitch_shift_f32(const smx_stft_config *c, const smx_resample_config *r, int phase, const float *x, int64_t lead, int64_t n,
+                        float *y) {
+  return guarded([&] { shift_host(c, r, phase, x, 4, lead, n, y); });
+}
+int smx_pitch_shift_f64(const smx_stft_config *c, const smx_resample_config *r, int phase, const double *x, int64_t lead, int64_t n,
+                        double *y) {
+  return guarded([&] { shift_host(c, r, phase, x, 8, lead, n, y); });
+}
+int smx_pitch_shift_f32_dev(const smx_stft_config *c, const smx_resample_config *r, int phase, const float *d_x, int64_t lead, int64_t n,
+                            float *d_y, void *stream) {
+  return guarded([&] {
+    check_shift(c, r, phase, lead, n);
+    shift_dev(*c, *r, phase, d_x, 4, lead, n, d_y, (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"

@@ -982,6 +982,7 @@ int smx_fir_apply_f32_dev(const smx_fir_plan *p, const float *d_x, int64_t chann
   });
 }
 
+// plain hipMalloc + hipMemcpy, not host_call: at these sizes its pooled scratch and staged copy measured slower (profiles/host_faces/NOTES.md)
 int smx_fir_apply_f32(const smx_fir_plan *p, const float *x, int64_t channels, int64_t n, float *y) {
   return guarded([&] {
     if (!p) throw Failure("fir_apply: null plan");
@@ -1352,6 +1353,7 @@ int smx_resample_shape_c128_dev(const double *d_x, const double *d_h, double *d_
   return guarded([&] { shape_dev(d_x, d_h, d_y, lines, n, sl, sm, (hipStream_t)stream); });
 }
 
+// plain hipMalloc + hipMemcpy, not host_call: at these sizes its pooled scratch and staged copy measured slower (profiles/host_faces/NOTES.md)
 int smx_resample_shape_c128(const double *x, const double *h, double *y, int64_t lines, int64_t n, int64_t sl, int64_t sm) {
   return guarded([&] {
     int64_t w = 0;
@@ -1421,6 +1423,7 @@ int smx_resample_stage_apply_f32_dev(const smx_resample_stage *s, const float *d
   });
 }
 
+// plain hipMalloc + hipMemcpy, not host_call: at these sizes its pooled scratch and staged copy measured slower (profiles/host_faces/NOTES.md)
 int smx_resample_stage_apply_f32(const smx_resample_stage *s, const float *x, int64_t channels, int64_t n, float *y) {
   return guarded([&] {
     if (!s) throw Failure("resample_stage: null stage");
@@ -1495,7 +1498,8 @@ int smx_resample_kernel_flush_f32_dev(smx_resample_kernel *k, float *d_y, int64_
     if (n_out) *n_out = got;
   });
 }
-/* host chunks [channels; n] (row stride x_stride) -> y [channels; *n_out] (row stride y_stride >= out_bound(n)) */
+/* host chunks [channels; n] (row stride x_stride) -> y [channels; *n_out] (row stride y_stride >= out_bound(n)); not a batch call
+   (strided rows, a length known only after the run), so step and flush keep their own copies instead of host_call */
 int smx_resample_kernel_step_f32(smx_resample_kernel *k, const float *x, int64_t n, int64_t x_stride, float *y, int64_t y_stride,
                                  int64_t *n_out) {
   return guarded([&] {

@@ -348,3 +348,194 @@ void launch_hpss(const HpssJob &job) {
 }
 
 }  // namespace smx
+
+// ---- the C ABI's side: Hpss ------------------------------------------------------------------------------------------------
+namespace smx {
+namespace {
+
+// ---- Hpss (hpss.ml:351-504): checks in the reference's order and words, then one launch ---------------------------------
+struct HpssParams {
+  const char *fn = "hpss";
+  int64_t kernel_h = 31, kernel_p = 31;
+  double power = 2.0, margin_h = 1.0, margin_p = 1.0;
+};
+
+// check_kernel, check_power, check_margin (hpss.ml:373-396); rank and dtype are what the entry point's signature states
+void check_hpss(const HpssParams &q) {
+  if (q.kernel_h < 1 || q.kernel_p < 1)
+    throw InvalidArgument(format("%s: cannot median-filter with a kernel of (%lld, %lld) (both kernel sizes must be at least 1)", q.fn,
+                                 (long long)q.kernel_h, (long long)q.kernel_p));
+  if (std::isnan(q.power) || q.power <= 0.0)
+    throw InvalidArgument(format("%s: cannot raise the mask to the power %g (power must be strictly positive, or infinite for a hard mask)",
+                                 q.fn, std::isnan(q.power) ? std::fabs(q.power) : q.power));
+  if (!(std::isfinite(q.margin_h) && std::isfinite(q.margin_p) && q.margin_h >= 1.0 && q.margin_p >= 1.0))
+    throw InvalidArgument(format("%s: cannot bias the decision by a margin of (%g, %g) (both margins must be finite and at least 1)", q.fn,
+                                 std::isnan(q.margin_h) ? std::fabs(q.margin_h) : q.margin_h,
+                                 std::isnan(q.margin_p) ? std::fabs(q.margin_p) : q.margin_p));
+}
+
+void check_hpss_plane(const HpssParams &q, int64_t lead, int64_t bins, int64_t frames) {
+  if (lead < 0 || bins < 0 || frames < 0)
+    throw Failure(format("%s: negative extent (lead %lld, bins %lld, frames %lld)", q.fn, (long long)lead, (long long)bins,
+                         (long long)frames));
+  check_hpss(q);
+}
+
+// hpss_masks / hpss_of_spectrogram / hpss_of_stft on device-resident planes; either result pointer may be null
+void hpss_dev(int mode, const HpssParams &q, const void *d_s, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, void *d_h,
+              void *d_p, hipStream_t stream) {
+  check_hpss_plane(q, lead, bins, frames);
+  if (lead == 0 || bins == 0 || frames == 0) return;   // nothing to separate
+  if (!d_s || (!d_h && !d_p)) throw Failure(format("%s: null device pointer", q.fn));
+  HpssJob job;
+  job.mode = mode;
+  job.s = d_s;
+  job.elem_bytes = elem_bytes;
+  job.lead = lead;
+  job.bins = bins;
+  job.frames = frames;
+  job.kernel_h = q.kernel_h;
+  job.kernel_p = q.kernel_p;
+  job.power = q.power;
+  job.margin_h = q.margin_h;
+  job.margin_p = q.margin_p;
+  job.out_h = d_h;
+  job.out_p = d_p;
+  job.stream = stream;
+  launch_hpss(job);
+}
+
+void hpss_host(int mode, const HpssParams &q, const void *s, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, void *h, void *p) {
+  check_hpss_plane(q, lead, bins, frames);
+  if (lead == 0 || bins == 0 || frames == 0) return;
+  if (!s || (!h && !p)) throw Failure(format("%s: null pointer", q.fn));
+  const size_t plane = (size_t)bins * (size_t)frames * (size_t)elem_bytes * (mode == HPSS_STFT ? 2 : 1);
+  host_call(q.fn, {{s, plane}}, {{h, plane}, {p, plane}}, lead, true, nullptr,
+            [&](const void *const *d_in, void *const *d_out, int64_t nc, hipStream_t stream) {
+              hpss_dev(mode, q, d_in[0], elem_bytes, nc, bins, frames, d_out[0], d_out[1], stream);
+            });
+}
+
+// `separate` (hpss.ml:477-492): Stft.transform -> hpss_of_stft -> Stft.invert ~length:n of the components that are wanted.  The
+// checks of all three run before any device work
+void check_separate(const HpssParams &q, const smx_stft_config *c, int64_t lead, int64_t n) {
+  check_hpss(q);
+  check_config(c, q.fn);
+  check_rank_extents(q.fn, lead, n);
+  check_synthesis("invert", *c, c->bins(), n, true);
+}
+
+// The three complex planes live in scratch and the batch goes through in clip chunks that keep them bounded: every clip is
+// analysed, separated and synthesised on its own (stft.mli:214-218), so a chunk's result is the slice of the whole batch's.
+void separate_dev(const HpssParams &q, const smx_stft_config &c, const void *d_x, int in_bytes, int64_t lead, int64_t n, void *d_h,
+                  void *d_p, hipStream_t stream) {
+  check_separate(q, &c, lead, n);
+  if (lead == 0 || n == 0) return;
+  if (!d_x || (!d_h && !d_p)) throw Failure(format("%s: null device pointer", q.fn));
+  const int64_t bins = c.bins(), frames = c.frames(n);
+  const size_t plane = (size_t)bins * (size_t)frames * 2 * (size_t)in_bytes;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(lead, (int64_t)(((size_t)256 << 20) / std::max<size_t>(plane, 1))));
+  init_device_pool();
+  DeviceScratch z, z_h, z_p;
+  z.pool(std::max<size_t>(16, (size_t)chunk * plane), stream);
+  if (d_h) z_h.pool(std::max<size_t>(16, (size_t)chunk * plane), stream);
+  if (d_p) z_p.pool(std::max<size_t>(16, (size_t)chunk * plane), stream);
+  const size_t row = (size_t)n * (size_t)in_bytes;
+  for (int64_t c0 = 0; c0 < lead; c0 += chunk) {
+    const int64_t nc = std::min(chunk, lead - c0);
+    stft_range_dev(c, reinterpret_cast<const unsigned char *>(d_x) + (size_t)c0 * row, in_bytes, nc, n, n, 0, frames, OUT_COMPLEX, 2.0,
+                   z.ptr, stream);
+    hpss_dev(HPSS_STFT, q, z.ptr, in_bytes, nc, bins, frames, z_h.ptr, z_p.ptr, stream);
+    if (d_h) invert_dev(c, z_h.ptr, 2 * in_bytes, nc, bins, frames, 1, n, reinterpret_cast<unsigned char *>(d_h) + (size_t)c0 * row, stream);
+    if (d_p) invert_dev(c, z_p.ptr, 2 * in_bytes, nc, bins, frames, 1, n, reinterpret_cast<unsigned char *>(d_p) + (size_t)c0 * row, stream);
+  }
+}
+
+void separate_host(const HpssParams &q, const smx_stft_config *c, const void *x, int in_bytes, int64_t lead, int64_t n, void *h, void *p) {
+  check_separate(q, c, lead, n);
+  if (lead == 0 || n == 0) return;
+  if (!x || (!h && !p)) throw Failure(format("%s: null pointer", q.fn));
+  const size_t row = (size_t)n * (size_t)in_bytes;
+  host_call(q.fn, {{x, row}}, {{h, row}, {p, row}}, lead, true, nullptr,
+            [&](const void *const *d_in, void *const *d_out, int64_t nc, hipStream_t stream) {
+              separate_dev(q, *c, d_in[0], in_bytes, nc, n, d_out[0], d_out[1], stream);
+            });
+}
+
+HpssParams hpss_params(const char *fn, int64_t kernel_h, int64_t kernel_p, double power, double margin_h, double margin_p) {
+  HpssParams q;
+  q.fn = fn;
+  q.kernel_h = kernel_h;
+  q.kernel_p = kernel_p;
+  q.power = power;
+  q.margin_h = margin_h;
+  q.margin_p = margin_p;
+  return q;
+}
+
+// the signal face's name: `hpss` returns the pair, `harmonic` / `percussive` one of them (hpss.ml:494-504)
+const char *separate_name(const void *h, const void *p) { return h && p ? "hpss" : (h ? "harmonic" : (p ? "percussive" : "hpss")); }
+
+}  // namespace
+}  // namespace smx
+
+using namespace smx;
+
+extern "C" {
+
+// ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------
+#define SMX_HPSS_ARGS int64_t kernel_h, int64_t kernel_p, double power, double margin_h, double margin_p
+#define SMX_HPSS_Q(fn) hpss_params(fn, kernel_h, kernel_p, power, margin_h, margin_p)
+int smx_hpss_masks_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *mask_h, float *mask_p) {
+  return guarded([&] { hpss_host(HPSS_MASKS, SMX_HPSS_Q("hpss_masks"), s, 4, lead, bins, frames, mask_h, mask_p); });
+}
+int smx_hpss_masks_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, double *mask_h, double *mask_p) {
+  return guarded([&] { hpss_host(HPSS_MASKS, SMX_HPSS_Q("hpss_masks"), s, 8, lead, bins, frames, mask_h, mask_p); });
+}
+int smx_hpss_masks_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *d_mask_h, float *d_mask_p,
+                           void *stream) {
+  return guarded([&] {
+    hpss_dev(HPSS_MASKS, SMX_HPSS_Q("hpss_masks"), d_s, 4, lead, bins, frames, d_mask_h, d_mask_p, (hipStream_t)stream);
+  });
+}
+int smx_hpss_of_spectrogram_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *h, float *p) {
+  return guarded([&] { hpss_host(HPSS_SPECTROGRAM, SMX_HPSS_Q("hpss_of_spectrogram"), s, 4, lead, bins, frames, h, p); });
+}
+int smx_hpss_of_spectrogram_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, double *h, double *p) {
+  return guarded([&] { hpss_host(HPSS_SPECTROGRAM, SMX_HPSS_Q("hpss_of_spectrogram"), s, 8, lead, bins, frames, h, p); });
+}
+int smx_hpss_of_spectrogram_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *d_h, float *d_p,
+                                    void *stream) {
+  return guarded([&] {
+    hpss_dev(HPSS_SPECTROGRAM, SMX_HPSS_Q("hpss_of_spectrogram"), d_s, 4, lead, bins, frames, d_h, d_p, (hipStream_t)stream);
+  });
+}
+int smx_hpss_of_stft_c64(const float *z, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *z_h, float *z_p) {
+  return guarded([&] { hpss_host(HPSS_STFT, SMX_HPSS_Q("hpss_of_stft"), z, 4, lead, bins, frames, z_h, z_p); });
+}
+int smx_hpss_of_stft_c128(const double *z, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, double *z_h, double *z_p) {
+  return guarded([&] { hpss_host(HPSS_STFT, SMX_HPSS_Q("hpss_of_stft"), z, 8, lead, bins, frames, z_h, z_p); });
+}
+int smx_hpss_of_stft_c64_dev(const float *d_z, int64_t lead, int64_t bins, int64_t frames, SMX_HPSS_ARGS, float *d_z_h, float *d_z_p,
+                             void *stream) {
+  return guarded([&] { hpss_dev(HPSS_STFT, SMX_HPSS_Q("hpss_of_stft"), d_z, 4, lead, bins, frames, d_z_h, d_z_p, (hipStream_t)stream); });
+}
+int smx_hpss_f32(const smx_stft_config *c, const float *x, int64_t lead, int64_t n, SMX_HPSS_ARGS, float *y_h, float *y_p) {
+  return guarded([&] { separate_host(SMX_HPSS_Q(separate_name(y_h, y_p)), c, x, 4, lead, n, y_h, y_p); });
+}
+int smx_hpss_f64(const smx_stft_config *c, const double *x, int64_t lead, int64_t n, SMX_HPSS_ARGS, double *y_h, double *y_p) {
+  return guarded([&] { separate_host(SMX_HPSS_Q(separate_name(y_h, y_p)), c, x, 8, lead, n, y_h, y_p); });
+}
+int smx_hpss_f32_dev(const smx_stft_config *c, const float *d_x, int64_t lead, int64_t n, SMX_HPSS_ARGS, float *d_y_h, float *d_y_p,
+                     void *stream) {
+  return guarded([&] {
+    const HpssParams q = SMX_HPSS_Q(separate_name(d_y_h, d_y_p));
+    check_hpss(q);
+    check_config(c, q.fn);
+    separate_dev(q, *c, d_x, 4, lead, n, d_y_h, d_y_p, (hipStream_t)stream);
+  });
+}
+#undef SMX_HPSS_ARGS
+#undef SMX_HPSS_Q
+
+}  // extern "C"

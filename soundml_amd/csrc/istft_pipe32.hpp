@@ -35,7 +35,7 @@
 //       envelope (float64 product, a division on the clip's first and last hops); 8-byte stores, 512 contiguous bytes per
 //       wave and hop; signal drained(it).
 // A frame gets the same bits wherever it sits and a position sums the same values in the same order whatever the tiling,
-// so the streaming synthesis (capi.cpp, which runs this kernel over [history ++ chunk]) totals Stft.invert bit for bit.
+// so the streaming synthesis (stft_stream.cpp, which runs this kernel over [history ++ chunk]) totals Stft.invert bit for bit.
 using f2 = float __attribute__((ext_vector_type(2)));
 #include "stft_pk_fft.inc"
 
@@ -54,7 +54,7 @@ struct PipeArgs {
   int64_t range_base, range_extra; // total_tiles / blocks and the remainder
   int blocks;
   int aligned_out;                 // every clip's output pairs are 8-byte aligned (out, out_len and left even)
-  // FM (Griffin-Lim's own spectra, capi.cpp): z, prev and mag FRAME-MAJOR -- [clip][frame][bin] in rows of fm_pitch elements,
+  // FM (Griffin-Lim's own spectra, griffinlim.hip): z, prev and mag FRAME-MAJOR -- [clip][frame][bin] in rows of fm_pitch elements,
   // fm_clip elements per clip (stft2048_complex_fm_kernel writes z / prev that way)
   int fm_pitch;
   int64_t fm_clip;

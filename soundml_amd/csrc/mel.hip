@@ -9,6 +9,8 @@
 // for 128 mels over 1025 bins that is ~1/3.8 of the dense K loop.
 // float64 (and float32 audio with the float64 interior): VALU dot products over
 // the band, float64 accumulation, one rounding -- the reference's arithmetic.
+#include <cstring>
+
 #include "smx_internal.hpp"
 
 namespace smx {
@@ -180,3 +182,191 @@ void launch_mel_apply(const MelJob &job) {
 }
 
 }  // namespace smx
+
+// ---- the C ABI's side: Mel.Config, Mel.apply, Soundml.mel_spectrogram ------------------------------------------------------
+namespace smx {
+namespace {
+
+void check_mel_shape(const smx_mel_config &c, int64_t lead, int64_t bins, int64_t frames) {
+  if (lead < 0 || frames < 0 || bins < 0) throw Failure("apply: negative extent");
+  if (bins != c.bins())  // mel.ml:210-218
+    throw InvalidArgument(format(
+        "apply: cannot project %lld frequency bins through a filterbank built for an FFT of size %lld "
+        "(%lld bins)",
+        (long long)bins, (long long)c.fft_size, (long long)c.bins()));
+}
+
+void mel_apply_dev(const smx_mel_config &c, const void *d_s, int elem_bytes, int64_t lead, int64_t bins,
+                   int64_t frames, void *d_out, hipStream_t stream) {
+  check_mel_shape(c, lead, bins, frames);
+  if (lead == 0 || frames == 0) return;  // mel.ml:220-226: nothing to reduce over
+  if (!d_s || !d_out) throw Failure("apply: null device pointer");
+  MelJob job;
+  job.cfg = &c;
+  job.s = d_s;
+  job.elem_bytes = elem_bytes;
+  job.lead = lead;
+  job.frames = frames;
+  job.out = d_out;
+  job.stream = stream;
+  launch_mel_apply(job);
+}
+
+void mel_apply_host(const smx_mel_config &c, const void *s, int elem_bytes, int64_t lead, int64_t bins,
+                    int64_t frames, void *out) {
+  check_mel_shape(c, lead, bins, frames);
+  if (lead == 0 || frames == 0) return;
+  if (!s || !out) throw Failure("apply: null pointer");
+  host_call("mel_apply", {{s, (size_t)bins * (size_t)frames * (size_t)elem_bytes}}, out, (size_t)c.n_mels * (size_t)frames * (size_t)elem_bytes,
+            lead, false, nullptr, [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mel_apply_dev(c, d_in[0], elem_bytes, nc, bins, frames, d_out, stream);
+            });
+}
+
+void check_fft_sizes(const smx_stft_config &sc, const smx_mel_config &mc) {  // soundml.ml:12-20
+  if (sc.fft_size != mc.fft_size)
+    throw InvalidArgument(format(
+        "mel_spectrogram: cannot project a %lld-point STFT through a filterbank built for an FFT of "
+        "size %lld (the two configurations must agree on fft_size)",
+        (long long)sc.fft_size, (long long)mc.fft_size));
+}
+
+}  // namespace
+
+// Soundml.mel_spectrogram on device-resident audio.  The fused kernel keeps the
+// power tile on chip; other geometries run power_spectrum into a scratch
+// spectrogram followed by Mel.apply (the reference's own composition).
+void mel_spectrogram_dev(const smx_stft_config &sc, const smx_mel_config &mc, const void *d_x,
+                         int in_bytes, int64_t lead, int64_t n, int64_t x_stride, double power,
+                         void *d_out, hipStream_t stream) {
+  check_fft_sizes(sc, mc);
+  check_rank_extents("mel_spectrogram", lead, n);
+  if (x_stride < n) throw Failure("mel_spectrogram: x_stride is smaller than the signal length");
+  const int64_t count = sc.frames(n);
+  if (lead == 0 || count == 0) return;
+  if (!d_x || !d_out) throw Failure("mel_spectrogram: null device pointer");
+  MelSpecJob job;
+  job.stft = stft_job(sc, d_x, in_bytes, lead, n, x_stride, 0, count, OUT_POWER, power, nullptr, stream);
+  job.mel = &mc;
+  job.out = d_out;
+  if (launch_mel_spectrogram_fused(job)) return;
+  // two-step form; scratch is stream-ordered
+  void *scratch = nullptr;
+  const size_t bytes = (size_t)lead * (size_t)sc.bins() * (size_t)count * (size_t)in_bytes;
+  SMX_HIP_CHECK(smx::pool_malloc_async(&scratch, bytes, stream));
+  job.stft.out = scratch;
+  launch_stft(job.stft);
+  mel_apply_dev(mc, scratch, in_bytes, lead, sc.bins(), count, d_out, stream);
+  SMX_HIP_CHECK(hipFreeAsync(scratch, stream));
+}
+
+namespace {
+
+// Soundml.mel_spectrogram from host memory: the current device, or the device list's clip ranges side by side (soundml.mli:85-101:
+// leading axes broadcast; mel_props.ml:136-155 tests the slices)
+void mel_spectrogram_host(const smx_stft_config &sc, const smx_mel_config &mc, const void *x, int in_bytes,
+                          int64_t lead, int64_t n, double power, void *out) {
+  check_fft_sizes(sc, mc);
+  check_rank_extents("mel_spectrogram", lead, n);
+  const int64_t count = sc.frames(n);
+  if (lead == 0 || count == 0) return;
+  if (!x || !out) throw Failure("mel_spectrogram: null pointer");
+  host_call("mel_spectrogram", {{x, (size_t)n * (size_t)in_bytes}}, out, (size_t)mc.n_mels * (size_t)count * (size_t)in_bytes, lead, true,
+            nullptr, [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mel_spectrogram_dev(sc, mc, d_in[0], in_bytes, nc, n, n, power, d_out, stream);
+            });
+}
+
+}  // namespace
+}  // namespace smx
+
+using namespace smx;
+
+extern "C" {
+
+int smx_mel_config_create(int64_t n_mels, int64_t sample_rate, int64_t fft_size, double f_min,
+                          int has_f_max, double f_max, int scale, int norm, smx_mel_config **out) {
+  return guarded([&] {
+    if (!out) throw Failure("create: null output handle");
+    *out = mel_config_create(n_mels, sample_rate, fft_size, f_min, has_f_max != 0, f_max, scale, norm);
+  });
+}
+int smx_mel_config_from_weights(int64_t rows, int64_t fft_size, const double *weights, smx_mel_config **out) {
+  return guarded([&] {
+    if (!out || !weights) throw Failure("from_weights: null pointer");
+    if (rows < 1) throw InvalidArgument(format("from_weights: cannot build %lld filters (rows must be at least 1)", (long long)rows));
+    if (fft_size < 1)
+      throw InvalidArgument(format("from_weights: cannot use an FFT of size %lld (fft_size must be at least 1)", (long long)fft_size));
+    smx_mel_config *c = new smx_mel_config();
+    c->n_mels = rows;
+    c->fft_size = fft_size;
+    c->weights.assign(weights, weights + (size_t)rows * (size_t)(fft_size / 2 + 1));
+    *out = c;
+  });
+}
+void smx_mel_config_destroy(smx_mel_config *c) { delete c; }
+int64_t smx_mel_config_n_mels(const smx_mel_config *c) { return c ? c->n_mels : -1; }
+int64_t smx_mel_config_bins(const smx_mel_config *c) { return c ? c->bins() : -1; }
+int64_t smx_mel_config_fft_size(const smx_mel_config *c) { return c ? c->fft_size : -1; }
+double smx_mel_config_f_max(const smx_mel_config *c) { return c ? c->f_max : -1.0; }
+int smx_mel_filterbank(const smx_mel_config *c, double *out) {
+  return guarded([&] {
+    check_config(c, "filterbank");
+    std::memcpy(out, c->weights.data(), c->weights.size() * sizeof(double));
+  });
+}
+int smx_mel_apply_f32(const smx_mel_config *c, const float *s, int64_t lead, int64_t bins,
+                      int64_t frames, float *out) {
+  return guarded([&] {
+    check_config(c, "apply");
+    mel_apply_host(*c, s, 4, lead, bins, frames, out);
+  });
+}
+int smx_mel_apply_f64(const smx_mel_config *c, const double *s, int64_t lead, int64_t bins,
+                      int64_t frames, double *out) {
+  return guarded([&] {
+    check_config(c, "apply");
+    mel_apply_host(*c, s, 8, lead, bins, frames, out);
+  });
+}
+int smx_mel_apply_f32_dev(const smx_mel_config *c, const float *d_s, int64_t lead, int64_t bins,
+                          int64_t frames, float *d_out, void *stream) {
+  return guarded([&] {
+    check_config(c, "apply");
+    mel_apply_dev(*c, d_s, 4, lead, bins, frames, d_out, (hipStream_t)stream);
+  });
+}
+int smx_mel_apply_f64_dev(const smx_mel_config *c, const double *d_s, int64_t lead, int64_t bins,
+                          int64_t frames, double *d_out, void *stream) {
+  return guarded([&] {
+    check_config(c, "apply");
+    mel_apply_dev(*c, d_s, 8, lead, bins, frames, d_out, (hipStream_t)stream);
+  });
+}
+int smx_mel_spectrogram_f32(const smx_stft_config *sc, const smx_mel_config *mc, const float *x,
+                            int64_t lead, int64_t n, double power, float *out) {
+  return guarded([&] {
+    check_config(sc, "mel_spectrogram");
+    check_config(mc, "mel_spectrogram");
+    mel_spectrogram_host(*sc, *mc, x, 4, lead, n, power, out);
+  });
+}
+int smx_mel_spectrogram_f64(const smx_stft_config *sc, const smx_mel_config *mc, const double *x,
+                            int64_t lead, int64_t n, double power, double *out) {
+  return guarded([&] {
+    check_config(sc, "mel_spectrogram");
+    check_config(mc, "mel_spectrogram");
+    mel_spectrogram_host(*sc, *mc, x, 8, lead, n, power, out);
+  });
+}
+int smx_mel_spectrogram_f32_dev(const smx_stft_config *sc, const smx_mel_config *mc, const float *d_x,
+                                int64_t lead, int64_t n, int64_t x_stride, double power, float *d_out,
+                                void *stream) {
+  return guarded([&] {
+    check_config(sc, "mel_spectrogram");
+    check_config(mc, "mel_spectrogram");
+    mel_spectrogram_dev(*sc, *mc, d_x, 4, lead, n, x_stride, power, d_out, (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"

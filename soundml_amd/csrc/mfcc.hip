@@ -439,3 +439,166 @@ void launch_mfcc(const MfccJob &job) {
 }
 
 }  // namespace smx
+
+// ---- the C ABI's side: Soundml.mfcc, Convert.power_to_db / amplitude_to_db -------------------------------------------------
+namespace smx {
+namespace {
+
+// Soundml.mfcc (soundml.ml:50-95): checks in the reference's order and words, then mel_spectrogram + the tail
+void check_mfcc(const smx_stft_config &sc, const smx_mel_config &mc, int64_t n_mfcc, int has_lifter, double lifter) {
+  if (sc.fft_size != mc.fft_size)
+    throw InvalidArgument(format(
+        "mfcc: cannot project a %lld-point STFT through a filterbank built for an FFT of size %lld (the two "
+        "configurations must agree on fft_size)",
+        (long long)sc.fft_size, (long long)mc.fft_size));
+  if (n_mfcc < 1 || n_mfcc > mc.n_mels)
+    throw InvalidArgument(format(
+        "mfcc: cannot keep %lld cepstral coefficients of %lld mel bands (n_mfcc must lie in [1, n_mels])",
+        (long long)n_mfcc, (long long)mc.n_mels));
+  if (has_lifter && !(std::isfinite(lifter) && lifter >= 0.0))
+    throw InvalidArgument(format("mfcc: cannot lifter with a coefficient of %g (lifter must be finite and non-negative)",
+                                 lifter));
+}
+
+void mfcc_dev(const smx_stft_config &sc, const smx_mel_config &mc, const void *d_x, int in_bytes, int64_t lead,
+              int64_t n, int64_t x_stride, int64_t n_mfcc, int has_lifter, double lifter, void *d_out,
+              hipStream_t stream) {
+  check_mfcc(sc, mc, n_mfcc, has_lifter, lifter);
+  check_rank_extents("mfcc", lead, n);
+  const int64_t count = sc.frames(n);
+  if (lead == 0 || count == 0) return;
+  if (!d_x || !d_out) throw Failure("mfcc: null device pointer");
+  void *mel = nullptr;
+  SMX_HIP_CHECK(smx::pool_malloc_async(&mel, (size_t)lead * (size_t)mc.n_mels * (size_t)count * (size_t)in_bytes, stream));
+  mel_spectrogram_dev(sc, mc, d_x, in_bytes, lead, n, x_stride, 2.0, mel, stream);
+  MfccJob job;
+  job.mel = mel;
+  job.elem_bytes = in_bytes;
+  job.lead = lead;
+  job.frames = count;
+  job.n_mels = (int)mc.n_mels;
+  job.n_mfcc = (int)n_mfcc;
+  job.lifter = has_lifter ? lifter : 0.0;
+  job.out = d_out;
+  job.stream = stream;
+  launch_mfcc(job);
+  SMX_HIP_CHECK(hipFreeAsync(mel, stream));
+}
+
+void mfcc_host(const smx_stft_config &sc, const smx_mel_config &mc, const void *x, int in_bytes, int64_t lead,
+               int64_t n, int64_t n_mfcc, int has_lifter, double lifter, void *out) {
+  check_mfcc(sc, mc, n_mfcc, has_lifter, lifter);
+  check_rank_extents("mfcc", lead, n);
+  const int64_t count = sc.frames(n);
+  if (lead == 0 || count == 0) return;
+  if (!x || !out) throw Failure("mfcc: null pointer");
+  host_call("mfcc", {{x, (size_t)n * (size_t)in_bytes}}, out, (size_t)n_mfcc * (size_t)count * (size_t)in_bytes, lead, false, nullptr,
+            [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mfcc_dev(sc, mc, d_in[0], in_bytes, nc, n, n, n_mfcc, has_lifter, lifter, d_out, stream);
+            });
+}
+
+// ---- Convert.power_to_db / amplitude_to_db (convert.ml:3-62) ------------------------------------------------
+void to_db_checks(const char *fn, double reference, double amin, int has_top_db, double top_db) {
+  if (!(std::isfinite(reference) && reference > 0.0))
+    throw InvalidArgument(format("Soundml.Convert.%s: reference must be finite and positive", fn));
+  if (!(std::isfinite(amin) && amin > 0.0))
+    throw InvalidArgument(format("Soundml.Convert.%s: amin must be finite and positive", fn));
+  if (has_top_db && !(std::isfinite(top_db) && top_db >= 0.0))
+    throw InvalidArgument(format("Soundml.Convert.%s: top_db must be finite and non-negative", fn));
+}
+
+void to_db_dev(bool amplitude, const void *d_s, int elem_bytes, int64_t total, double reference, double amin, int has_top_db,
+               double top_db, void *d_out, hipStream_t stream) {
+  const char *fn = amplitude ? "amplitude_to_db" : "power_to_db";
+  to_db_checks(fn, reference, amin, has_top_db, top_db);
+  if (total < 0) throw Failure(format("%s: negative extent", fn));
+  if (total == 0) return;
+  if (!d_s || !d_out) throw Failure(format("%s: null device pointer", fn));
+  ToDbJob job;
+  job.s = d_s;
+  job.out = d_out;
+  job.elem_bytes = elem_bytes;
+  job.total = total;
+  job.gain = amplitude ? 20.0 : 10.0;
+  job.magnitude = amplitude;
+  job.reference = reference;
+  job.amin = amin;
+  job.has_top_db = has_top_db != 0;
+  job.top_db = top_db;
+  job.stream = stream;
+  launch_to_db(job);
+}
+
+// in place on ONE device array: host_call would hold an input and a result array, twice the device memory
+void to_db_host(bool amplitude, const void *s, int elem_bytes, int64_t total, double reference, double amin, int has_top_db,
+                double top_db, void *out) {
+  to_db_checks(amplitude ? "amplitude_to_db" : "power_to_db", reference, amin, has_top_db, top_db);
+  if (total <= 0) return;
+  if (!s || !out) throw Failure("to_db: null pointer");
+  require_device();
+  const size_t bytes = (size_t)total * (size_t)elem_bytes;
+  DeviceScratch d(bytes);
+  copy_to_device(d.ptr, s, bytes);
+  to_db_dev(amplitude, d.ptr, elem_bytes, total, reference, amin, has_top_db, top_db, d.ptr, nullptr);
+  SMX_HIP_CHECK(hipStreamSynchronize(nullptr));
+  copy_to_host(out, d.ptr, bytes);
+}
+
+}  // namespace
+}  // namespace smx
+
+using namespace smx;
+
+extern "C" {
+
+// ---- Convert.power_to_db / amplitude_to_db (convert.ml:52-62) ------------------------------------------
+int smx_power_to_db_f32(const float *s, int64_t total, double reference, double amin, int has_top_db, double top_db, float *out) {
+  return guarded([&] { to_db_host(false, s, 4, total, reference, amin, has_top_db, top_db, out); });
+}
+int smx_power_to_db_f64(const double *s, int64_t total, double reference, double amin, int has_top_db, double top_db, double *out) {
+  return guarded([&] { to_db_host(false, s, 8, total, reference, amin, has_top_db, top_db, out); });
+}
+int smx_power_to_db_f32_dev(const float *d_s, int64_t total, double reference, double amin, int has_top_db, double top_db,
+                            float *d_out, void *stream) {
+  return guarded([&] { to_db_dev(false, d_s, 4, total, reference, amin, has_top_db, top_db, d_out, (hipStream_t)stream); });
+}
+int smx_amplitude_to_db_f32(const float *s, int64_t total, double reference, double amin, int has_top_db, double top_db, float *out) {
+  return guarded([&] { to_db_host(true, s, 4, total, reference, amin, has_top_db, top_db, out); });
+}
+int smx_amplitude_to_db_f64(const double *s, int64_t total, double reference, double amin, int has_top_db, double top_db,
+                            double *out) {
+  return guarded([&] { to_db_host(true, s, 8, total, reference, amin, has_top_db, top_db, out); });
+}
+int smx_amplitude_to_db_f32_dev(const float *d_s, int64_t total, double reference, double amin, int has_top_db, double top_db,
+                                float *d_out, void *stream) {
+  return guarded([&] { to_db_dev(true, d_s, 4, total, reference, amin, has_top_db, top_db, d_out, (hipStream_t)stream); });
+}
+
+// ---- Soundml.mfcc (soundml.ml:50-95) --------------------------------------------------------------
+int smx_mfcc_f32(const smx_stft_config *sc, const smx_mel_config *mc, const float *x, int64_t lead, int64_t n,
+                 int64_t n_mfcc, int has_lifter, double lifter, float *out) {
+  return guarded([&] {
+    check_config(sc, "mfcc");
+    check_config(mc, "mfcc");
+    mfcc_host(*sc, *mc, x, 4, lead, n, n_mfcc, has_lifter, lifter, out);
+  });
+}
+int smx_mfcc_f64(const smx_stft_config *sc, const smx_mel_config *mc, const double *x, int64_t lead, int64_t n,
+                 int64_t n_mfcc, int has_lifter, double lifter, double *out) {
+  return guarded([&] {
+    check_config(sc, "mfcc");
+    check_config(mc, "mfcc");
+    mfcc_host(*sc, *mc, x, 8, lead, n, n_mfcc, has_lifter, lifter, out);
+  });
+}
+int smx_mfcc_f32_dev(const smx_stft_config *sc, const smx_mel_config *mc, const float *d_x, int64_t lead, int64_t n,
+                     int64_t x_stride, int64_t n_mfcc, int has_lifter, double lifter, float *d_out, void *stream) {
+  return guarded([&] {
+    check_config(sc, "mfcc");
+    check_config(mc, "mfcc");
+    mfcc_dev(*sc, *mc, d_x, 4, lead, n, x_stride, n_mfcc, has_lifter, lifter, d_out, (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"

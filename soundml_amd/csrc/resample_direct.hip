@@ -422,6 +422,7 @@ int smx_resample_apply_f32_dev(const smx_resample_config *c, const float *d_x, i
   });
 }
 
+// plain hipMalloc + hipMemcpy, not host_call: at these sizes its pooled scratch and staged copy measured slower (profiles/host_faces/NOTES.md)
 int smx_resample_apply_f32(const smx_resample_config *c, const float *x, int64_t channels, int64_t n, float *y) {
   return guarded([&] {
     if (!c) throw Failure("resample: null config");
@@ -493,6 +494,7 @@ int smx_resample_stream_flush_f32_dev(smx_resample_stream *k, float *d_y, int64_
     if (n_out) *n_out = got;
   });
 }
+// the host forms of step and flush are not batch calls (strided rows, a length known only after the run): no host_call
 int smx_resample_stream_step_f32(smx_resample_stream *k, const float *x, int64_t n, int64_t x_stride, float *y, int64_t y_stride,
                                  int64_t *n_out) {
   return guarded([&] {

@@ -281,6 +281,34 @@ int device_cu_count();                               // compute units of the CUR
 void pipelined_host_call(const void *src, size_t in_clip_bytes, void *dst, size_t out_clip_bytes, int64_t clips, int64_t unit,
                          void *d_in, void *d_out, const std::function<void(int64_t, int64_t, hipStream_t)> &launch);
 
+// One input array of a host-pointer call: clip_bytes per clip.  A null host pointer is an absent optional input: no device copy,
+// and the device function sees a null pointer.
+struct HostIn {
+  const void *host;
+  size_t clip_bytes;
+};
+// One result array of a host-pointer call: clip_bytes per clip.  A null host pointer is a result the caller does not want: no device
+// copy, no download, and the device function sees a null pointer.
+struct HostOut {
+  void *host;
+  size_t clip_bytes;
+};
+// The host-pointer form of a batch call of `lead` clips whose arguments the caller has checked (capi.cpp): require_device, then per
+// clip range device copies of the inputs and of the results, upload, dev(d_in, d_out, nclips, stream), download.  dev enqueues the
+// work of nclips clips on `stream` with d_in[i] / d_out[i] at their first clip.
+//   shard     the device list's clip ranges side by side (smx_set_devices)
+//   pipeline  (one input, one result) a large batch is cut into units of clips whose upload, kernels and download overlap
+//             (pipelined_host_call; a unit's result is the slice of the whole call's bit for bit: the reference's per-slice law,
+//             stft_grid.ml:180-205), this configuration's tables built first.  SMX_HOST_PIPELINE=0: serially.
+void host_call(const char *name, const std::vector<HostIn> &in, const std::vector<HostOut> &out, int64_t lead, bool shard,
+               const smx_stft_config *pipeline, const std::function<void(const void *const *, void *const *, int64_t, hipStream_t)> &dev);
+// the common case: one result array
+inline void host_call(const char *name, const std::vector<HostIn> &in, void *out, size_t out_clip, int64_t lead, bool shard,
+                      const smx_stft_config *pipeline, const std::function<void(const void *const *, void *, int64_t, hipStream_t)> &dev) {
+  host_call(name, in, {HostOut{out, out_clip}}, lead, shard, pipeline,
+            [&](const void *const *d_in, void *const *d_out, int64_t nc, hipStream_t stream) { dev(d_in, d_out[0], nc, stream); });
+}
+
 // ---- host logic (host_config.cpp) ----------------------------------------------
 void window_make(int kind, bool periodic, int64_t n, double *out);             // window.ml:374-405
 void window_make_param(int kind, double param, bool periodic, int64_t n, double *out);   // Kaiser / Gaussian / Tukey too
@@ -378,7 +406,7 @@ struct IstftJob {
   // frames (no tail region: every position read is settled, stft.ml:1137-1142)
   int64_t left = -1, env_q0 = 0, env_count = 0;
   bool env_open = false;
-  // Griffin-Lim's own spectra (capi.cpp): z, prev and mag FRAME-MAJOR, [lead; fm_rows; fm_pitch] elements (fm_pitch > 0; fft 2048 /
+  // Griffin-Lim's own spectra (griffinlim.hip): z, prev and mag FRAME-MAJOR, [lead; fm_rows; fm_pitch] elements (fm_pitch > 0; fft 2048 /
   // hop 512 / complex64 / float32 interior on the persistent pipeline only: istft_frame_major_ok(job))
   int64_t fm_pitch = 0, fm_rows = 0;
 };
@@ -535,7 +563,24 @@ struct MelSpecJob {
 bool launch_mel_spectrogram_fused(const MelSpecJob &job);   // stft_fast.hip; false = not eligible
 bool launch_mel_spectrogram_16(const MelSpecJob &job);      // stft_generic.hip: fft 512 / 1024
 
-// ---- the C ABI's entry points (capi.cpp, fir.hip) ----------------------------------------------------------------
+// ---- host glue shared between the modules (capi.cpp unless named; one definition each) ------------------------------
+int interior();                                                          // the library's interior (smx_set_interior)
+void check_config(const void *c, const char *fn);
+void check_rank_extents(const char *fn, int64_t lead, int64_t n);
+StftJob stft_job(const smx_stft_config &c, const void *x, int in_bytes, int64_t lead, int64_t n, int64_t x_stride, int64_t p0,
+                 int64_t count, OutMode mode, double power, void *out, hipStream_t stream);
+void stft_range_dev(const smx_stft_config &c, const void *d_x, int in_bytes, int64_t lead, int64_t n, int64_t x_stride, int64_t p0,
+                    int64_t p1, OutMode mode, double power, void *d_out, hipStream_t stream);
+void check_synthesis(const char *op, const smx_stft_config &c, int64_t bins, int64_t length, bool has_length);
+void invert_dev(const smx_stft_config &c, const void *d_z, int z_bytes, int64_t lead, int64_t bins, int64_t frames, int has_length,
+                int64_t length, void *d_out, hipStream_t stream);
+void mel_spectrogram_dev(const smx_stft_config &sc, const smx_mel_config &mc, const void *d_x, int in_bytes, int64_t lead, int64_t n,
+                         int64_t x_stride, double power, void *d_out, hipStream_t stream);                            // mel.hip
+void check_chroma_norm(const char *op, int norm, double norm_p);                                                      // spectral.hip
+void chroma_apply_dev(const smx_chroma_config &c, const void *d_s, int elem_bytes, int64_t lead, int64_t bins, int64_t frames,
+                      int norm, double norm_p, void *d_out, hipStream_t stream);                                      // spectral.hip
+
+// ---- the C ABI's entry points (each module's own file) --------------------------------------------------------------
 // body() as one entry point: InvalidArgument -> SMX_INVALID_ARGUMENT, any other exception -> SMX_FAILURE, its text in smx_last_error
 template <typename F>
 int guarded(F &&body) {

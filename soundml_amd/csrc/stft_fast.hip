@@ -712,7 +712,7 @@ bool launch_stft_fast(const StftJob &job) {
   return true;
 }
 
-// Griffin-Lim's analysis step (capi.cpp): the complex spectrum of every frame of the request frame-major -- out[clip][frame][bin] in
+// Griffin-Lim's analysis step (griffinlim.hip): the complex spectrum of every frame of the request frame-major -- out[clip][frame][bin] in
 // rows of pitch_floats floats, rows_per_clip (= a multiple of 16, at least the frames) rows a clip.  false = not taken (the caller
 // keeps the reference layout): fft 2048 / float32 interior only, and a request whose border frames can ride in the tile sequence.
 bool launch_stft_complex_fm(const StftJob &job, void *out, int64_t pitch_floats, int64_t rows_per_clip, bool only_ask) {

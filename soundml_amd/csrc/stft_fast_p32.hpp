@@ -1575,7 +1575,7 @@ __global__ void __launch_bounds__(512) stft2048_complex32_kernel(FastArgs a) {
 }
 
 // ---- the spectrum FRAME-MAJOR: out[clip][frame][k], k < 1025, rows of `a.out_stride` floats (Griffin-Lim's rebuilt spectra, which
-// only this library's own synthesis reads: capi.cpp).  A lane holds bins l + 32 s and 1024 - l - 32 s of its frame, so 32 lanes
+// only this library's own synthesis reads: griffinlim.hip).  A lane holds bins l + 32 s and 1024 - l - 32 s of its frame, so 32 lanes
 // store 256 contiguous bytes of the frame's row per slot straight from their registers: no tile, no flush, no counters -- the
 // frame's column of LDS carries its transposition and exchange only, and the waves of a workgroup never wait for each other.
 // Every clip owns tiles_per_clip x 16 rows: the frames a clip's last tile does not have land in rows nobody reads.
