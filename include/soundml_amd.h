@@ -21,6 +21,12 @@
  *     hipStream_t (as void*); they enqueue work and return without
  *     synchronising.  The host-pointer entry points upload, run and download
  *     (this is what an nx-tensor caller uses).
+ *   - placement of the `*_dev` buffers: any pointer aligned to its element type
+ *     (float: 4 bytes, double and complex64: 8, complex128: 16) is valid -- no
+ *     entry point asks for more; a row stride is in elements and >= the row's
+ *     length n; what lies between the rows, before the first and behind the
+ *     last one is the caller's: it is neither read into a result nor written
+ *     (tests/test_gpu_placement.py).
  *   - every extent is validated before any pointer is formed or any device
  *     work is enqueued (discipline of resample_stubs.c:228-276).
  *   - the library never falls back to a CPU implementation: without a HIP
