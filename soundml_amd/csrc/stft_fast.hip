@@ -17,9 +17,11 @@
 // persistent workgroup per CU walking a contiguous range of the flat (clip, tile) sequence (TileWalk below), waves meeting at
 // monotonic LDS counters instead of barriers.  (The 64-lane kernels of rounds 1-2 -- in-wave transposes by permlane / DPP -- are gone.)
 //
-// Frames that reach past either end of the signal: their tile takes its samples through the padding rule (FastArgs::fold_frames
-// == 2, load_frame32_padded / load_frameL_padded: round 5); for clips shorter than a frame, from gathered, already padded strips
-// (fold_frames == 1) or the power kernels' border epilogue.
+// Frames that reach past either end of the signal ride in the tile sequence of the one launch (launch_ranges): their tile takes its
+// samples through the padding rule (FastArgs::fold_frames == 2, load_frame32_padded / load_frameL_padded: round 5).  Where that
+// rule does not reach (fft 4096, clips of 2^30 samples and more, SMX_BORDER_INLINE=0) they come from gathered, already padded
+// strips (fold_frames == 1) or, few of them in a power launch, from the power kernels' border epilogue; a request without an
+// interior frame is one strip through the STRIP instantiations.
 //
 // Algorithmic HBM bytes per frame at fft 2048 / hop 512: power 2048 + 4100 = 6148 B, complex 2048 + 8200 = 10248 B,
 // mel 2048 + 4 n_mels.
@@ -29,6 +31,7 @@
 
 #include "fft_device.hpp"
 #include "smx_internal.hpp"
+#include "stft_sample.hpp"
 
 namespace smx {
 namespace {
@@ -225,6 +228,62 @@ struct TileWalk {
   }
 };
 
+// The frame lookup of every kernel below, stated once: callable objects that a kernel sets up like the lambdas they replace
+// (they hold the arguments by reference and are optimised on their own before the kernel takes them in; free __forceinline__
+// functions compute the same values from a perturbed register allocation).
+// First sample of frame fi of tile t (FT frames a tile) of the clip at xc.  fi is the lane's frame, a reference to the kernel's
+// own L.col (32-lane kernels: 2 * wave + L.h; lanes kernels) or wave (stft4096_power64_kernel); a lane without a frame re-reads
+// the tile's first frame and its results are never stored.  fold_frames == 1: a frame that touches a border of the signal comes from its gathered, already
+// padded strip; fold_frames == 2: the pointer may lie outside the clip -- then only its position is used (load_frame*_padded).
+template <int FT>
+struct FrameSource {
+  const FastArgs &a;
+  const int &fi;
+  __device__ __forceinline__ const float *operator()(const float *xc, int t) const {
+    const int64_t f0 = (int64_t)t * FT;
+    const int avail = (int)(a.count - f0 < FT ? a.count - f0 : FT) - 1;   // last frame of the tile that exists (wave-uniform)
+    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
+    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
+      const int64_t clip = (xc - a.x) / a.x_stride;
+      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
+                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
+    }
+    return xc + (p * a.hop - a.left);
+  }
+};
+// fold_frames == 2, 32-lane kernels: one of THIS WAVE's two frames of tile t reaches past the signal, so the wave takes
+// load_frame32_padded for the tile (wave-uniform).  Only this wave takes the padding rule, the other waves of such a tile keep
+// the plain requests: a C2 clip's first tile has its border frames on wave 0, its last one on wave 4, and with the whole tile
+// on the padding rule the prologue's requests alone took 4.7 us (profiles/r07/timeline_prologue_pieces.log).
+// SHARE (load_pair32_shared): a wave without frames reads the tile's frames 0 AND 1.
+template <bool SHARE>
+struct WaveBorder32 {
+  const FastArgs &a;
+  const int &wave;
+  __device__ __forceinline__ bool operator()(int t) const {
+    if (a.fold_frames != 2) return false;
+    const int64_t f0 = (int64_t)t * kFT;
+    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
+    bool any = false;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int fi = 2 * wave + hh;
+      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : (SHARE ? hh : 0));
+      any = any || p < a.border_i0 || p >= a.border_i1;
+    }
+    return any;
+  }
+};
+// ... lanes kernels (a wave holds several frames of the tile's FT): the whole tile takes load_frameL_padded
+template <int FT>
+struct TileBorderLanes {
+  const FastArgs &a;
+  __device__ __forceinline__ bool operator()(int t) const {
+    const int64_t q0 = a.p0 + (int64_t)t * FT;
+    return a.fold_frames == 2 && (q0 < a.border_i0 || q0 + FT > a.border_i1);
+  }
+};
+
 #ifndef SMX_WAIT_SLEEP
 #define SMX_WAIT_SLEEP 2
 #endif
@@ -284,28 +343,8 @@ __global__ void __launch_bounds__(256) gather_padded_kernel(const float *x, int6
   const int64_t clip = blockIdx.y, pos0 = sp.pos0, len = sp.len;
   const float *src = x + clip * x_stride;
   float *dst = sp.out + clip * sp.out_stride;
-  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256) {
-    int64_t s = pos0 + j;
-    float v;
-    if (s >= 0 && s < n) {
-      v = src[s];
-    } else if (pad == SMX_PAD_REFLECT) {
-      if (n == 1) {
-        s = 0;
-      } else {
-        const int64_t period = 2 * (n - 1);
-        int64_t m = s % period;
-        if (m < 0) m += period;
-        s = m < n ? m : period - m;
-      }
-      v = src[s];
-    } else if (pad == SMX_PAD_EDGE) {
-      v = src[s < 0 ? 0 : n - 1];
-    } else {
-      v = pad_value;
-    }
-    dst[j] = v;
-  }
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < len; j += (int64_t)gridDim.x * 256)
+    dst[j] = (float)fetch_sample(src, n, pos0 + j, pad, (double)pad_value);   // the boundary rule, stated once (stft_sample.hpp)
 }
 
 // What a launch produces: the power spectrogram (mel == nullptr) or the fused mel spectrogram.
@@ -317,11 +356,14 @@ struct FastTarget {
   const Mel32Args *mel32 = nullptr;   // with mel: the 32-lane kernel's plan (nullptr: the 64-lane kernel)
   bool complex_out = false;     // Stft.transform: interleaved (re, im)
   bool frame_major = false;     // ... as out[clip][frame][bin] in rows of out_stride floats, tiles_per_clip x 16 rows a clip (Griffin-Lim's own spectra)
-  // power kernel only: border frames folded into the interior launch (see stft2048_power_kernel's epilogue)
+  // frames outside [border_i0, border_i1) touch a border of the signal.  One launch over every frame of the request:
+  bool fold_frames = false;     // ... they come from gathered strips (FastArgs::fold_frames == 1)
+  bool inline_border = false;   // ... they load through the padding rule (FastArgs::fold_frames == 2; round 5)
+  int64_t border_i0 = 0, border_i1 = 0;
+  // power kernels only, a launch over the interior frames: border_left + border_right border frames a clip, from frame border_p0
+  // on, are computed after the interior tiles (the kernels' epilogue)
   int border_left = 0, border_right = 0;
-  int64_t border_p0 = 0, border_i1 = 0;
-  bool fold_frames = false;     // complex / mel kernels: one launch over every frame of the request (FastArgs::fold_frames)
-  bool inline_border = false;   // power kernel at fft 2048 (round 5): one launch over every frame, the border tiles load through the padding rule (FastArgs::fold_frames == 2)
+  int64_t border_p0 = 0;
   const float *strip_l = nullptr, *strip_r = nullptr;
   int64_t strip_l_stride = 0, strip_r_stride = 0;
 };
@@ -381,23 +423,23 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
   a.border_left = strip ? 0 : tg.border_left;
   a.border_right = strip ? 0 : tg.border_right;
   a.border_p0 = tg.border_p0;
-  a.border_i1 = tg.border_i1;
   a.border_out_offset = tg.out_offset;
   a.fold_frames = strip ? 0 : tg.inline_border ? 2 : tg.fold_frames ? 1 : 0;
-  a.border_i0 = tg.border_p0;   // folded complex / mel launches: border_p0 carries the first interior frame
+  a.border_i0 = tg.border_i0;
+  a.border_i1 = tg.border_i1;
   a.strip_l = tg.strip_l;
   a.strip_r = tg.strip_r;
   a.strip_l_stride = tg.strip_l_stride;
   a.strip_r_stride = tg.strip_r_stride;
   const bool aligned = (c.hop % 2 == 0) && (left % 2 == 0) && (x_stride % 2 == 0) &&
                        (reinterpret_cast<uintptr_t>(x) % 8 == 0);
-  const bool square = a.pmode == 2;
+  // the launch itself: a.blocks persistent workgroups of kernel k with `lds` bytes of dynamic LDS
+  auto launch = [&](auto k, size_t lds, const auto &...more) { launch_tiles("stft", k, a.blocks, 512, lds, job.stream, a, more...); };
   if (p64) {
     if (tg.complex_out || tg.mel) throw Failure("stft: the fft-4096 pipeline has the power face only");
     // a.interleave as chosen above (2 chip-wide / 1 per XCD): this kernel's 32-byte row runs need the neighbouring tiles written at the
     // same time (stft_fast_p64.hpp); SMX_P64_CONTIGUOUS=1 in diagnostic builds: contiguous ranges (A/B timing: 0.74 against 0.54 ms)
     if (diag_flag("SMX_P64_CONTIGUOUS") == 1) a.interleave = 0;
-    a.pmode = job.power == 2.0 ? 2 : (job.power == 1.0 ? 1 : 0);
     const bool even = a.out_stride % 2 == 0 && ((reinterpret_cast<uintptr_t>(a.out) >> 2) + (uintptr_t)a.out_offset) % 2 == 0 &&
                       reinterpret_cast<uintptr_t>(a.out) % 8 == 0;
     auto by_power = [&](auto al, auto ev) {
@@ -406,22 +448,17 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
     };
     auto by_al = [&](auto ev) { return aligned ? by_power(std::true_type{}, ev) : by_power(std::false_type{}, ev); };
     auto k64 = even ? by_al(std::true_type{}) : by_al(std::false_type{});
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k64Lds));
-    SMX_LAUNCH(k64, dim3((unsigned)a.blocks), dim3(512), k64Lds, job.stream, a);
-    SMX_HIP_CHECK(hipGetLastError());
-    return;
+    return launch(k64, k64Lds);
   }
   if (lanes && tg.complex_out) {   // Stft.transform at fft 1024 / 512 / 256
     auto launch_cplx_lanes = [&](auto ll) {
       constexpr int LL = decltype(ll)::value;
       auto kl = aligned ? stft_complex_lanes_kernel<LL, true> : stft_complex_lanes_kernel<LL, false>;
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PL<LL>::Lds));
-      SMX_LAUNCH(kl, dim3((unsigned)a.blocks), dim3(512), PL<LL>::Lds, job.stream, a);
+      launch(kl, PL<LL>::Lds);
     };
     if (lanes == 16) launch_cplx_lanes(std::integral_constant<int, 16>{});
     else if (lanes == 8) launch_cplx_lanes(std::integral_constant<int, 8>{});
     else launch_cplx_lanes(std::integral_constant<int, 4>{});
-    SMX_HIP_CHECK(hipGetLastError());
     return;
   }
   if (lanes >= 8 && tg.mel32) {   // fused mel at fft 1024 / 512
@@ -435,12 +472,10 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
       };
       auto by_al = [&](auto fr) { return aligned ? by_power(std::true_type{}, fr) : by_power(std::false_type{}, fr); };
       auto kl = m.four == 2 ? by_al(std::true_type{}) : by_al(std::false_type{});
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PL<LL>::Lds));
-      SMX_LAUNCH(kl, dim3((unsigned)a.blocks), dim3(512), PL<LL>::Lds, job.stream, a, m);
+      launch(kl, PL<LL>::Lds, m);
     };
     if (lanes == 16) launch_mel_lanes(std::integral_constant<int, 16>{});
     else launch_mel_lanes(std::integral_constant<int, 8>{});
-    SMX_HIP_CHECK(hipGetLastError());
     return;
   }
   if (lanes) {
@@ -470,13 +505,11 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
           kl = aligned ? by_power(std::true_type{}) : by_power(std::false_type{});
         }
       }
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PL<LL>::Lds));
-      SMX_LAUNCH(kl, dim3((unsigned)a.blocks), dim3(512), PL<LL>::Lds, job.stream, a);
+      launch(kl, PL<LL>::Lds);
     };
     if (lanes == 16) launch_lanes(std::integral_constant<int, 16>{});
     else if (lanes == 8) launch_lanes(std::integral_constant<int, 8>{});
     else launch_lanes(std::integral_constant<int, 4>{});
-    SMX_HIP_CHECK(hipGetLastError());
     return;
   }
   if (tg.mel && tg.mel32) {
@@ -489,17 +522,11 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
     };
     auto by_al = [&](auto fr) { return aligned ? by_power(std::true_type{}, fr) : by_power(std::false_type{}, fr); };
     auto k32 = m.four == 2 ? by_al(std::integral_constant<int, 2>{}) : m.four == 1 ? by_al(std::integral_constant<int, 1>{}) : by_al(std::integral_constant<int, 0>{});
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
-    SMX_LAUNCH(k32, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a, m);
-    SMX_HIP_CHECK(hipGetLastError());
-    return;
+    return launch(k32, kFast32Lds, m);
   }
   if (tg.complex_out && tg.frame_major) {   // the spectrum frame-major, straight from the registers (stft_fast_p32.hpp: stft2048_complex_fm_kernel)
     auto kf = aligned ? stft2048_complex_fm_kernel<true> : stft2048_complex_fm_kernel<false>;
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
-    SMX_LAUNCH(kf, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a);
-    SMX_HIP_CHECK(hipGetLastError());
-    return;
+    return launch(kf, kFast32Lds);
   }
   if (tg.complex_out) {   // Stft.transform on the 32-lane frame pipeline
     // the flush in whole aligned 128-byte lines (stft_fast_p32.hpp, cplx_skew32_*): consecutive tiles of a clip on one workgroup
@@ -507,10 +534,7 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
     if (cskew) a.interleave = 0;
     auto k32 = cskew ? (aligned ? stft2048_complex32_kernel<true, true> : stft2048_complex32_kernel<false, true>)
                      : (aligned ? stft2048_complex32_kernel<true, false> : stft2048_complex32_kernel<false, false>);
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
-    SMX_LAUNCH(k32, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a);
-    SMX_HIP_CHECK(hipGetLastError());
-    return;
+    return launch(k32, kFast32Lds);
   }
 #ifdef SMX_DIAG
   if (diag_flag("SMX_NOSTORE") == 1) a.abl_nostore = 1;   // timing-only ablations of the 32-lane kernel (results wrong by construction)
@@ -519,7 +543,6 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
   if ((a.abl_p32 & 1) && !((p0 + kFT) * c.hop - left >= 0 && (p0 + 2 * kFT - 1) * c.hop - left + kN <= n && count >= 2 * kFT && !strip))
     throw Failure("stft: SMX_P32_ABL=1 needs a request whose second tile lies inside the clip");
 #endif
-  (void)square;
   // The power spectrogram at fft 2048: the 32-lane frame pipeline (stft_fast_p32.hpp).
   {
     auto pick32 = [&](auto strip_tag) {
@@ -548,10 +571,7 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
         return a.pmode == 2 ? stft2048_power32_kernel<true, 2, false, K, true> : a.pmode == 1 ? stft2048_power32_kernel<true, 1, false, K, true> : stft2048_power32_kernel<true, 0, false, K, true>;
       };
       auto k32p = skew == 1 ? by_power(std::integral_constant<int, 1>{}) : skew == 2 ? by_power(std::integral_constant<int, 2>{}) : by_power(std::integral_constant<int, 0>{});
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k32p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
-      SMX_LAUNCH(k32p, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a);
-      SMX_HIP_CHECK(hipGetLastError());
-      return;
+      return launch(k32p, kFast32Lds);
     }
     if (skew) {
       a.interleave = 0;
@@ -562,35 +582,40 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
       };
       auto by_al = [&](auto sk) { return aligned ? by_power(std::true_type{}, sk) : by_power(std::false_type{}, sk); };
       auto k32s = skew == 1 ? by_al(std::integral_constant<int, 1>{}) : by_al(std::integral_constant<int, 2>{});
-      SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k32s), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
-      SMX_LAUNCH(k32s, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a);
-      SMX_HIP_CHECK(hipGetLastError());
-      return;
+      return launch(k32s, kFast32Lds);
     }
     auto k32 = strip ? pick32(std::true_type{}) : pick32(std::false_type{});
-    SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFast32Lds));
-    SMX_LAUNCH(k32, dim3((unsigned)a.blocks), dim3(512), kFast32Lds, job.stream, a);
-    SMX_HIP_CHECK(hipGetLastError());
-    return;
+    launch(k32, kFast32Lds);
   }
 }
 
-// frames [pa, pb) that touch a border: gather their padded span, then run the fused kernel on it
-void launch_border(const StftJob &job, const FastTarget &tg, int64_t pa, int64_t pb) {
-  if (pb <= pa) return;
+// one strip: the padded span of frames [pa, pb) of every clip, allocated on the job's stream (pb <= pa: no strip, len 0)
+GatherSpan alloc_strip(const StftJob &job, int64_t pa, int64_t pb) {
+  GatherSpan sp{};
+  if (pb <= pa) return sp;
   const smx_stft_config &c = *job.cfg;
-  const int64_t pos0 = pa * c.hop - job.left;               // signal position of the strip's first sample
-  const int64_t len = (pb - pa - 1) * c.hop + c.fft_size;
-  const int64_t stride = (len + 1) & ~int64_t(1);            // even: keeps 8-byte aligned rows
-  float *strip = nullptr;
-  SMX_HIP_CHECK(smx::pool_malloc_async((void **)&strip, (size_t)job.lead * (size_t)stride * sizeof(float), job.stream));
-  dim3 grid((unsigned)((len + 255) / 256 < 64 ? (len + 255) / 256 : 64), (unsigned)job.lead);
-  const GatherSpan span{pos0, len, stride, strip};
-  SMX_LAUNCH(gather_padded_kernel, grid, dim3(256), 0, job.stream, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, span, span,
+  sp.pos0 = pa * c.hop - job.left;                    // signal position of the strip's first sample
+  sp.len = (pb - pa - 1) * c.hop + c.fft_size;
+  sp.out_stride = (sp.len + 1) & ~int64_t(1);         // even: keeps 8-byte aligned rows
+  SMX_HIP_CHECK(smx::pool_malloc_async((void **)&sp.out, (size_t)job.lead * (size_t)sp.out_stride * sizeof(float), job.stream));
+  return sp;
+}
+// fills `count` strips (1: s0; 2: s0 and s1) in ONE launch (a span of length 0 has no work)
+void gather_strips(const StftJob &job, const GatherSpan &s0, const GatherSpan &s1, unsigned count) {
+  const int64_t longest = s0.len > s1.len ? s0.len : s1.len;
+  dim3 grid((unsigned)((longest + 255) / 256 < 64 ? (longest + 255) / 256 : 64), (unsigned)job.lead, count);
+  SMX_LAUNCH(gather_padded_kernel, grid, dim3(256), 0, job.stream, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, s0, s1,
              job.pad, (float)job.pad_value);
   SMX_HIP_CHECK(hipGetLastError());
-  launch_interior(job, tg, strip, len, stride, 0, 0, pb - pa, tg.out_offset + (pa - job.p0), /*strip=*/true);
-  SMX_HIP_CHECK(hipFreeAsync(strip, job.stream));
+}
+
+// frames [pa, pb), none of them inside the signal: gather their padded span, then run the fused kernel on it
+void launch_border(const StftJob &job, const FastTarget &tg, int64_t pa, int64_t pb) {
+  if (pb <= pa) return;
+  const GatherSpan span = alloc_strip(job, pa, pb);
+  gather_strips(job, span, span, 1);
+  launch_interior(job, tg, span.out, span.len, span.out_stride, 0, 0, pb - pa, tg.out_offset + (pa - job.p0), /*strip=*/true);
+  SMX_HIP_CHECK(hipFreeAsync(span.out, job.stream));
 }
 
 bool fast_eligible(const StftJob &job, bool power_face = false) {
@@ -605,89 +630,71 @@ bool fast_eligible(const StftJob &job, bool power_face = false) {
   return true;
 }
 
-// splits frames [p0, p0 + count) into left border / interior / right border launches
-void launch_ranges(const StftJob &job, const FastTarget &tg) {
+// the frames of the request that lie inside the signal, [i0, i1) (i1 <= i0: none): frame p does iff 0 <= p*hop - left and
+// p*hop - left + N <= n
+struct InteriorRange {
+  int64_t i0, i1;
+};
+InteriorRange interior_range(const StftJob &job) {
   const smx_stft_config &c = *job.cfg;
-  // frame p lies inside the signal iff 0 <= p*hop - left and p*hop - left + N <= n
   const int64_t p0 = job.p0, p1 = job.p0 + job.count;
   int64_t i0 = job.left > 0 ? (job.left + c.hop - 1) / c.hop : 0;
   int64_t i1 = job.n + job.left - c.fft_size >= 0 ? (job.n + job.left - c.fft_size) / c.hop + 1 : 0;
   if (i0 < p0) i0 = p0;
   if (i1 > p1) i1 = p1;
-  if (i1 <= i0) {          // no interior frame in range: one strip for everything
-    launch_border(job, tg, p0, p1);
-    return;
-  }
-  // power spectrogram: the border frames ride in the interior launch (no gathers, no extra launches) whenever
-  // 32-bit sample positions suffice for the padding rule
-  static const bool fold_off = diag_flag("SMX_NO_BORDER_FOLD") == 1;
-  // ... while the border frames of the whole batch are few (C2: 1024 of 240 128).  Batches of many short clips (16 384 one-second
-  // clips: 65 536 border frames of 524 288) take the gathered strips below instead: the epilogue's barrier-separated tiles and
-  // element-wise stores cost them more than the whole interior (2.76 ms against 1.1).
-  const int64_t border_total = job.lead * ((i0 - p0) + (p1 - i1));
-  static const int64_t epilogue_max = (int64_t)diag_int("SMX_BORDER_EPILOGUE_MAX", 20000);
-  // Round 5, fft 2048: the border frames ride in the tile sequence itself -- ONE launch over every frame of the request, a tile
-  // that holds such a frame takes its samples through the padding rule (load_frame32_padded: one reflection, hence n >= fft).
-  // The epilogue below ran 4 tile times deep on a quarter of the workgroups at C2: 30 of the launch's 495 us
-  // (profiles/r07/timeline_before.log).  SMX_BORDER_INLINE=0: the epilogue / strips as before (same values: tested).
-  // (the complex spectrogram and the fused mel kernel at fft 2048 the same way: no gather launches before them)
-  // (and the fft 1024 / 512 / 256 kernels of stft_fast_p16.hpp: load_frameL_padded)
-  if ((c.fft_size == kN || c.fft_size == kN16 || c.fft_size == kN8 || c.fft_size == kN4) && (i0 - p0) + (p1 - i1) > 0 && job.n >= c.fft_size &&
-      job.n < (int64_t(1) << 30) && env_flag("SMX_BORDER_INLINE") != 0) {
-    FastTarget folded = tg;
+  return {i0, i1};
+}
+// the padding rule of load_frame32_padded / load_frameL_padded serves the request's border frames: one reflection (n >= fft) at
+// 32-bit sample positions.  SMX_BORDER_INLINE=0: gathered strips instead (same values: tested)
+bool border_inline_ok(const StftJob &job) {
+  return job.n >= job.cfg->fft_size && job.n < (int64_t(1) << 30) && env_flag("SMX_BORDER_INLINE") != 0;
+}
+
+// frames [p0, p0 + count) of the request: ONE launch of the fused kernel wherever an interior frame exists (a strip for the whole
+// request where none does; no border frame: a plain launch; the padding rule where it reaches; few border frames of a power
+// launch: the kernels' epilogue; otherwise gathered strips)
+void launch_ranges(const StftJob &job, const FastTarget &tg) {
+  const smx_stft_config &c = *job.cfg;
+  const int64_t p0 = job.p0, p1 = job.p0 + job.count;
+  const auto [i0, i1] = interior_range(job);
+  const float *x = reinterpret_cast<const float *>(job.x);
+  if (i1 <= i0) return launch_border(job, tg, p0, p1);   // no interior frame in range: one strip for everything
+  if (i0 == p0 && i1 == p1) return launch_interior(job, tg, x, job.n, job.x_stride, job.left, p0, p1 - p0, tg.out_offset);
+  FastTarget folded = tg;
+  folded.border_i0 = i0;
+  folded.border_i1 = i1;
+  // Round 5: the border frames ride in the tile sequence itself -- a tile that holds such a frame takes its samples through the
+  // padding rule.  (The epilogue below ran 4 tile times deep on a quarter of the workgroups at C2: 30 of the launch's 495 us,
+  // profiles/r07/timeline_before.log.)  Every face at fft 2048 and the fft 1024 / 512 / 256 kernels of stft_fast_p16.hpp; no
+  // gather launches before them.
+  if ((c.fft_size == kN || c.fft_size == kN16 || c.fft_size == kN8 || c.fft_size == kN4) && border_inline_ok(job)) {
     folded.inline_border = true;
-    folded.border_p0 = i0;
-    folded.border_i1 = i1;
-    launch_interior(job, folded, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, job.left, p0, p1 - p0, tg.out_offset);
-    return;
+    return launch_interior(job, folded, x, job.n, job.x_stride, job.left, p0, p1 - p0, tg.out_offset);
   }
-  if (!tg.mel && !tg.complex_out && !fold_off && job.n < (int64_t(1) << 30) && (i0 - p0) + (p1 - i1) > 0 &&
-      (i0 - p0) + (p1 - i1) < 4096 && border_total <= epilogue_max && c.fft_size != k64N) {   // (fft 4096: gathered strips, below)
-    FastTarget folded = tg;
+  // The power kernels' epilogue (SMX_BORDER_INLINE=0 reaches it; not fft 4096): the border frames are computed after the interior
+  // tiles of a launch over the interior frames, while those of the whole batch are few (C2: 1024 of 240 128).  Batches of many
+  // short clips (16 384 one-second clips: 65 536 border frames of 524 288) take the gathered strips below instead: the epilogue's
+  // barrier-separated tiles and element-wise stores cost them more than the whole interior (2.76 ms against 1.1).
+  static const int64_t epilogue_max = (int64_t)diag_int("SMX_BORDER_EPILOGUE_MAX", 20000);
+  if (!tg.mel && !tg.complex_out && job.n < (int64_t(1) << 30) && (i0 - p0) + (p1 - i1) < 4096 &&
+      job.lead * ((i0 - p0) + (p1 - i1)) <= epilogue_max && c.fft_size != k64N) {
     folded.border_left = (int)(i0 - p0);
     folded.border_right = (int)(p1 - i1);
     folded.border_p0 = p0;
-    folded.border_i1 = i1;
-    launch_interior(job, folded, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, job.left, i0, i1 - i0,
-                    tg.out_offset + (i0 - p0));
-    return;
+    return launch_interior(job, folded, x, job.n, job.x_stride, job.left, i0, i1 - i0, tg.out_offset + (i0 - p0));
   }
-  // complex spectrogram / fused mel: ONE launch of the fused kernel over the whole request; the border frames' padded
-  // spans are gathered first (two small launches) and the kernel takes those frames from the strips (C3: 0.66 -> 0.60 ms)
-  if (!fold_off && (i0 - p0) + (p1 - i1) > 0) {   // (the power kernel too when the epilogue above was not taken)
-    FastTarget folded = tg;
-    folded.fold_frames = true;
-    folded.border_p0 = i0;
-    folded.border_i1 = i1;
-    float *strips[2] = {nullptr, nullptr};
-    GatherSpan spans[2] = {};
-    auto plan = [&](int which, int64_t pa, int64_t pb, const float *&dst, int64_t &dst_stride) {
-      if (pb <= pa) return;
-      const int64_t pos0 = pa * c.hop - job.left, len = (pb - pa - 1) * c.hop + c.fft_size;
-      const int64_t stride = (len + 1) & ~int64_t(1);            // even: keeps 8-byte aligned rows
-      SMX_HIP_CHECK(smx::pool_malloc_async((void **)&strips[which], (size_t)job.lead * (size_t)stride * sizeof(float), job.stream));
-      spans[which] = GatherSpan{pos0, len, stride, strips[which]};
-      dst = strips[which];
-      dst_stride = stride;
-    };
-    plan(0, p0, i0, folded.strip_l, folded.strip_l_stride);
-    plan(1, i1, p1, folded.strip_r, folded.strip_r_stride);
-    {   // both strips in ONE launch (a span of length 0 has no work)
-      const int64_t longest = spans[0].len > spans[1].len ? spans[0].len : spans[1].len;
-      dim3 grid((unsigned)((longest + 255) / 256 < 64 ? (longest + 255) / 256 : 64), (unsigned)job.lead, 2);
-      SMX_LAUNCH(gather_padded_kernel, grid, dim3(256), 0, job.stream, reinterpret_cast<const float *>(job.x), job.n, job.x_stride,
-                 spans[0], spans[1], job.pad, (float)job.pad_value);
-      SMX_HIP_CHECK(hipGetLastError());
-    }
-    launch_interior(job, folded, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, job.left, p0, p1 - p0, tg.out_offset);
-    for (float *sp : strips)
-      if (sp) SMX_HIP_CHECK(hipFreeAsync(sp, job.stream));
-    return;
-  }
-  launch_border(job, tg, p0, i0);
-  launch_interior(job, tg, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, job.left, i0, i1 - i0,
-                  tg.out_offset + (i0 - p0));
-  launch_border(job, tg, i1, p1);
+  // Otherwise (fft 4096, complex / mel launches, many border frames): the border frames' padded spans are gathered first (both
+  // strips in one small launch) and the kernel takes those frames from the strips (C3: 0.66 -> 0.60 ms against launches of their own)
+  folded.fold_frames = true;
+  const GatherSpan left = alloc_strip(job, p0, i0), right = alloc_strip(job, i1, p1);
+  folded.strip_l = left.out;
+  folded.strip_l_stride = left.out_stride;
+  folded.strip_r = right.out;
+  folded.strip_r_stride = right.out_stride;
+  gather_strips(job, left, right, 2);
+  launch_interior(job, folded, x, job.n, job.x_stride, job.left, p0, p1 - p0, tg.out_offset);
+  for (float *sp : {left.out, right.out})
+    if (sp) SMX_HIP_CHECK(hipFreeAsync(sp, job.stream));
 }
 
 }  // namespace
@@ -721,13 +728,10 @@ bool launch_stft_complex_fm(const StftJob &job, void *out, int64_t pitch_floats,
   if (job.count <= 0 || job.lead <= 0) return true;
   if (rows_per_clip != (job.count + kFT - 1) / kFT * kFT || pitch_floats < 2 * (kN / 2 + 1) || pitch_floats % 2 != 0) return false;
   const int64_t p0 = job.p0, p1 = job.p0 + job.count;
-  int64_t i0 = job.left > 0 ? (job.left + c.hop - 1) / c.hop : 0;
-  int64_t i1 = job.n + job.left - c.fft_size >= 0 ? (job.n + job.left - c.fft_size) / c.hop + 1 : 0;
-  if (i0 < p0) i0 = p0;
-  if (i1 > p1) i1 = p1;
+  const auto [i0, i1] = interior_range(job);
   if (i1 <= i0) return false;
   const bool border = (i0 - p0) + (p1 - i1) > 0;
-  if (border && !(job.n >= c.fft_size && job.n < (int64_t(1) << 30) && env_flag("SMX_BORDER_INLINE") != 0)) return false;
+  if (border && !border_inline_ok(job)) return false;
   if (only_ask) return true;
   FastTarget tg;
   tg.complex_out = true;
@@ -737,7 +741,7 @@ bool launch_stft_complex_fm(const StftJob &job, void *out, int64_t pitch_floats,
   tg.out_offset = 0;
   if (border) {
     tg.inline_border = true;
-    tg.border_p0 = i0;
+    tg.border_i0 = i0;
     tg.border_i1 = i1;
   }
   launch_interior(job, tg, reinterpret_cast<const float *>(job.x), job.n, job.x_stride, job.left, p0, p1 - p0, 0);

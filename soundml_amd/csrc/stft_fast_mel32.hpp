@@ -538,31 +538,8 @@ __global__ void __launch_bounds__(512) stft2048_mel32_kernel(FastArgs a, Mel32Ar
   TileWalk tw;
   tw.init(a, m.out + m.out_offset, (int64_t)m.n_mels * m.out_stride);
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
-  auto frame_ptr = [&](const float *xc, int t) {   // as stft2048_power32_kernel
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
-    const int fi = 2 * wave + L.h;
-    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);
-  };
-  auto tile_border = [&](int t) {   // fold_frames == 2 (as stft2048_power32_kernel): one of this wave's two frames of tile t reaches past the signal
-    if (a.fold_frames != 2) return false;
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
-    bool any = false;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int fi = 2 * wave + hh;
-      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-      any = any || p < a.border_i0 || p >= a.border_i1;
-    }
-    return any;
-  };
+  const FrameSource<kFT> frame_ptr{a, L.col};
+  const WaveBorder32<false> tile_border{a, wave};
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);

@@ -579,28 +579,13 @@ __global__ void __launch_bounds__(512) stft_power_lanes_kernel(FastArgs a) {
   tw.init(a, a.out + a.out_offset, P::Bins * a.out_stride);
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
 
-  // first sample of this lane's frame in tile t of the clip at xc (lanes without a frame re-read the tile's first frame and
-  // their results are never stored)
-  auto frame_ptr = [&](const float *xc, int t) {
-    const int64_t f0 = (int64_t)t * P::FT;
-    const int avail = (int)(a.count - f0 < P::FT ? a.count - f0 : P::FT) - 1;   // last frame of the tile that exists (wave-uniform)
-    const int fi = L.col;
-    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);
-  };
+  // this lane's frame of tile t of the clip at xc, and whether the tile takes the padding rule (stft_fast.hip)
+  const FrameSource<P::FT> frame_ptr{a, L.col};
 
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);
-  auto tile_border = [&](int t) {   // fold_frames == 2 (as stft2048_power32_kernel): the tile takes load_frameL_padded
-    const int64_t q0 = a.p0 + (int64_t)t * P::FT;
-    return a.fold_frames == 2 && (q0 < a.border_i0 || q0 + P::FT > a.border_i1);
-  };
+  const TileBorderLanes<P::FT> tile_border{a};
   if (ntiles > 0) {
     const float *src0 = frame_ptr(tw.xclip, tw.ft);
     if (tile_border(tw.ft)) load_frameL_padded<LL>(a, tw.xclip, (int)(src0 - tw.xclip), L.l, raw);
@@ -769,25 +754,11 @@ __global__ void __launch_bounds__(512) stft_mel_lanes_kernel(FastArgs a, Mel32Ar
   TileWalk tw;
   tw.init(a, m.out + m.out_offset, (int64_t)m.n_mels * m.out_stride);
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
-  auto frame_ptr = [&](const float *xc, int t) {   // as stft_power_lanes_kernel
-    const int64_t f0 = (int64_t)t * P::FT;
-    const int avail = (int)(a.count - f0 < P::FT ? a.count - f0 : P::FT) - 1;
-    const int fi = L.col;
-    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);
-  };
+  const FrameSource<P::FT> frame_ptr{a, L.col};
+  const TileBorderLanes<P::FT> tile_border{a};
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);
-  auto tile_border = [&](int t) {   // fold_frames == 2 (as stft2048_power32_kernel): the tile takes load_frameL_padded
-    const int64_t q0 = a.p0 + (int64_t)t * P::FT;
-    return a.fold_frames == 2 && (q0 < a.border_i0 || q0 + P::FT > a.border_i1);
-  };
   if (ntiles > 0) {
     const float *src0 = frame_ptr(tw.xclip, tw.ft);
     if (tile_border(tw.ft)) load_frameL_padded<LL>(a, tw.xclip, (int)(src0 - tw.xclip), L.l, raw);
@@ -936,25 +907,11 @@ __global__ void __launch_bounds__(512) stft_complex_lanes_kernel(FastArgs a) {
   TileWalk tw;
   tw.init(a, a.out + 2 * a.out_offset, 2 * (int64_t)P::Bins * a.out_stride);
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
-  auto frame_ptr = [&](const float *xc, int t) {   // as stft_power_lanes_kernel
-    const int64_t f0 = (int64_t)t * P::FT;
-    const int avail = (int)(a.count - f0 < P::FT ? a.count - f0 : P::FT) - 1;
-    const int fi = L.col;
-    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);
-  };
+  const FrameSource<P::FT> frame_ptr{a, L.col};
+  const TileBorderLanes<P::FT> tile_border{a};
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);
-  auto tile_border = [&](int t) {   // fold_frames == 2 (as stft2048_power32_kernel): the tile takes load_frameL_padded
-    const int64_t q0 = a.p0 + (int64_t)t * P::FT;
-    return a.fold_frames == 2 && (q0 < a.border_i0 || q0 + P::FT > a.border_i1);
-  };
   if (ntiles > 0) {
     const float *src0 = frame_ptr(tw.xclip, tw.ft);
     if (tile_border(tw.ft)) load_frameL_padded<LL>(a, tw.xclip, (int)(src0 - tw.xclip), L.l, raw);

@@ -1101,20 +1101,8 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
   const unsigned long long tl_p2 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  // first sample of this lane's frame in tile t of the clip at xc (a lane-half without a frame re-reads the tile's
-  // first frame and its results are never stored)
-  auto frame_ptr = [&](const float *xc, int t) {
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;   // last frame of the tile that exists (wave-uniform)
-    const int fi = 2 * wave + L.h;
-    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);   // (fold_frames == 2: possibly outside the clip -- then only its position is used)
-  };
+  // this lane's frame of tile t of the clip at xc, and whether this wave takes the padding rule for the tile (stft_fast.hip)
+  const FrameSource<kFT> frame_ptr{a, L.col};
   // SHARE: first sample of this wave's frame pair in tile t (wave-uniform; a wave without frames takes the tile's first two,
   // which exist: the count is even)
   auto span_ptr = [&](const float *xc, int t) {
@@ -1123,23 +1111,7 @@ __global__ void __launch_bounds__(512) stft2048_power32_kernel(FastArgs a) {
     const int fi = 2 * wave;
     return xc + ((a.p0 + f0 + (fi <= avail ? fi : 0)) * a.hop - a.left);
   };
-  // fold_frames == 2: one of THIS WAVE's two frames of tile t reaches past the signal: the wave takes load_frame32_padded for
-  // the tile (wave-uniform; the other waves of such a tile keep the plain requests -- a C2 clip's first tile has its border
-  // frames on wave 0, its last one on wave 4: with the whole tile on the padding rule the prologue's requests alone took
-  // 4.7 us, profiles/r07/timeline_prologue_pieces.log)
-  auto tile_border = [&](int t) {
-    if (a.fold_frames != 2) return false;
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
-    bool any = false;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int fi = 2 * wave + hh;
-      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : (SHARE ? hh : 0));   // (SHARE: a wave without frames reads the tile's frames 0 AND 1)
-      any = any || p < a.border_i0 || p >= a.border_i1;
-    }
-    return any;
-  };
+  const WaveBorder32<SHARE> tile_border{a, wave};
 
   float2 raw[32];
 #pragma unroll
@@ -1494,31 +1466,8 @@ __global__ void __launch_bounds__(512) stft2048_complex32_kernel(FastArgs a) {
   TileWalk tw;
   tw.init(a, a.out + 2 * a.out_offset, 2 * kBins * a.out_stride);
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
-  auto frame_ptr = [&](const float *xc, int t) {   // as stft2048_power32_kernel
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
-    const int fi = 2 * wave + L.h;
-    const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);
-  };
-  auto tile_border = [&](int t) {   // fold_frames == 2 (as stft2048_power32_kernel): one of this wave's two frames of tile t reaches past the signal
-    if (a.fold_frames != 2) return false;
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
-    bool any = false;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int fi = 2 * wave + hh;
-      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-      any = any || p < a.border_i0 || p >= a.border_i1;
-    }
-    return any;
-  };
+  const FrameSource<kFT> frame_ptr{a, L.col};
+  const WaveBorder32<false> tile_border{a, wave};
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);
@@ -1619,26 +1568,14 @@ __global__ void __launch_bounds__(512) stft2048_complex_fm_kernel(FastArgs a) {
   TileWalk tw;
   tw.init(a, a.out, (int64_t)a.tiles_per_clip * kFT * a.out_stride);
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
-  auto frame_ptr = [&](const float *xc, int t) {   // as stft2048_power32_kernel (the border frames ride in the tile sequence or there are none)
+  auto frame_ptr = [&](const float *xc, int t) {   // FrameSource without the strips: the border frames ride in the tile sequence or there are none
     const int64_t f0 = (int64_t)t * kFT;
     const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
     const int fi = 2 * wave + L.h;
     const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
     return xc + (p * a.hop - a.left);
   };
-  auto tile_border = [&](int t) {
-    if (a.fold_frames != 2) return false;
-    const int64_t f0 = (int64_t)t * kFT;
-    const int avail = (int)(a.count - f0 < kFT ? a.count - f0 : kFT) - 1;
-    bool any = false;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int fi = 2 * wave + hh;
-      const int64_t p = a.p0 + f0 + (fi <= avail ? fi : 0);
-      any = any || p < a.border_i0 || p >= a.border_i1;
-    }
-    return any;
-  };
+  const WaveBorder32<false> tile_border{a, wave};
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);

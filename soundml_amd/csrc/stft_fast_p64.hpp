@@ -356,17 +356,7 @@ __global__ void __launch_bounds__(512) stft4096_power64_kernel(FastArgs a) {
   const int ntiles = tw.ntiles > 0 ? tw.ntiles : 0;
   // first sample of this wave's frame in tile t of the clip at xc (a wave without a frame re-reads the tile's first frame; its column is
   // never stored); fold_frames == 1: a frame that touches a border of the signal comes from a gathered, already padded strip
-  auto frame_ptr = [&](const float *xc, int t) {
-    const int64_t f0 = (int64_t)t * k64FT;
-    const int avail = (int)(a.count - f0 < k64FT ? a.count - f0 : k64FT) - 1;
-    const int64_t p = a.p0 + f0 + (wave <= avail ? wave : 0);
-    if (a.fold_frames == 1 && (p < a.border_i0 || p >= a.border_i1)) {
-      const int64_t clip = (xc - a.x) / a.x_stride;
-      return p < a.border_i0 ? a.strip_l + clip * a.strip_l_stride + (p - a.p0) * a.hop
-                             : a.strip_r + clip * a.strip_r_stride + (p - a.border_i1) * a.hop;
-    }
-    return xc + (p * a.hop - a.left);
-  };
+  const FrameSource<k64FT> frame_ptr{a, wave};
   float2 raw[32];
 #pragma unroll
   for (int j = 0; j < 32; ++j) raw[j] = make_float2(0.f, 0.f);

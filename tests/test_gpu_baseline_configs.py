@@ -311,9 +311,10 @@ print(json.dumps(out))
 
 @pytest.mark.timeout(600)
 def test_many_short_clips_take_the_strip_path_and_agree():
-    """6000 clips of 4000 samples: 8 frames each, 4 of them touching a border -- 24 000 border frames, above the launcher's
-    threshold, so the power kernel reads them from gathered strips (one launch over every frame) instead of its epilogue.
-    The same clips in a batch of 50 take the epilogue: identical frame code, so the values agree bit for bit; and three clips
+    """6000 clips of 4000 samples: 8 frames each, 4 of them touching a border -- 24 000 border frames in one launch.  As
+    shipped the border tiles ride in the tile sequence, in the big batch and in a batch of 50 alike (when the test was written
+    the big batch took the gathered strips and the small one the border epilogue, hence its name; with SMX_BORDER_INLINE=0 in
+    the environment they still do).  Identical frame code on another tile walk, so the values agree bit for bit; and three clips
     are checked against the oracle.  Mel and complex outputs of the big batch against small batches too."""
     import torch
     rng = np.random.default_rng(11)

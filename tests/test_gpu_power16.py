@@ -107,8 +107,9 @@ def test_batch_is_the_stack_of_its_slices(fft):
 
 @pytest.mark.parametrize("fft", [1024, 512, 256])
 def test_many_short_clips_take_the_strip_path_and_agree(fft):
-    """8000 clips of 8 frames each, 4 touching a border -- above the launcher's epilogue threshold, so the kernel reads the
-    border frames from gathered strips; the same clips in a batch of 50 take the epilogue: identical frame code."""
+    """8000 clips of 8 frames each, 4 touching a border.  As shipped the border tiles ride in the tile sequence, in the big
+    batch and in a batch of 50 alike (when the test was written the big batch took the gathered strips and the small one the
+    border epilogue, hence its name; with SMX_BORDER_INLINE=0 in the environment they still do): identical frame code."""
     import torch
     rng = np.random.default_rng(11)
     x = torch.from_numpy(rng.uniform(-1, 1, size=(8000, 2000 * fft // 1024)).astype(np.float32)).cuda()
