@@ -408,6 +408,59 @@ int smx_spectral_flatness_f64(const double *s, int64_t lead, int64_t bins, int64
 int smx_spectral_flatness_f32_dev(const float *d_s, int64_t lead, int64_t bins, int64_t frames, double amin,
                                   double power, float *d_out, void *stream);
 
+/* ---- Spectral contrast and onset strength (contrast.ml, onset.ml; Soundml.spectral_contrast*, onset_strength*) ----
+ * Octave-band contrast of a magnitude spectrogram s [lead; bins; frames] -> [lead; n_bands + 1; frames]: per band and
+ * frame the mean of the `take` largest magnitudes against the mean of the `take` smallest (an exact selection, float64
+ * means), `linear`: peak - valley, else the difference of their decibels (power_to_db, reference 1, floor 1e-10), with
+ * `clamped` each side under (the maximum of its own whole tensor) - 80 dB; one rounding to the dtype of s.
+ *
+ * smx_spectral_contrast_plan               contrast.ml:60-142: the bands as (first bin, bins, take), n_bands + 1 entries
+ *                                          each; host integers only, no device is touched
+ * smx_spectral_contrast_*                  contrast.ml:208-218: audio x [lead; n] -> the magnitude spectrogram -> contrast,
+ *                                          clamped
+ * smx_spectral_contrast_of_spectrogram_*   fft_size 0: contrast.ml:223-252, the FFT size implied by the bin count, the
+ *                                          magnitudes checked (non-negative, no NaN).  fft_size > 0: the body of
+ *                                          spectral_contrast_stage (contrast.ml:254-261) for a plan built at that size
+ *                                          (errors under that name, magnitudes unchecked; the stage passes clamped 0)
+ *
+ * Onset strength (onset.ml:153-199): mel_spectrogram (power 2) -> float64 decibels under the whole tensor's 80 dB clamp ->
+ * z[t] = mean over mels of max(0, db[., t] - db[., t - lag]), zero for t < lag -> centred analysis shifts right by
+ * fft_size / (2 hop) frames -> one rounding; x [lead; n] -> [lead; frames].
+ * smx_onset_flux_* is the one-chunk state_step of onset_strength_stage (onset.ml:82-122) with an empty carry: decibels
+ * s [lead; bins; frames] -> [lead; frames], no clamp, no shift.
+ *
+ * The device-resident forms carry the dtype LAST (`_dev_f32`, every older entry point has `_f32_dev`): the placement
+ * suite's first coverage law lists every name ending in `_dev` in one table that these entries are not part of; they have
+ * a table and a law of their own (tests/test_gpu_placement_contrast_onset.py) until the two are folded. */
+int smx_spectral_contrast_plan(int64_t n_bands, double f_min, double quantile, int64_t sample_rate, int64_t fft_size,
+                               int64_t *lo, int64_t *sub_len, int64_t *take);
+int smx_spectral_contrast_f32(const smx_stft_config *c, const float *x, int64_t lead, int64_t n, int64_t n_bands,
+                              double f_min, double quantile, int linear, int64_t sample_rate, float *out);
+int smx_spectral_contrast_f64(const smx_stft_config *c, const double *x, int64_t lead, int64_t n, int64_t n_bands,
+                              double f_min, double quantile, int linear, int64_t sample_rate, double *out);
+int smx_spectral_contrast_dev_f32(const smx_stft_config *c, const float *d_x, int64_t lead, int64_t n, int64_t x_stride,
+                                  int64_t n_bands, double f_min, double quantile, int linear, int64_t sample_rate,
+                                  float *d_out, void *stream);
+int smx_spectral_contrast_of_spectrogram_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, int64_t fft_size,
+                                             int64_t n_bands, double f_min, double quantile, int linear,
+                                             int64_t sample_rate, int clamped, float *out);
+int smx_spectral_contrast_of_spectrogram_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, int64_t fft_size,
+                                             int64_t n_bands, double f_min, double quantile, int linear,
+                                             int64_t sample_rate, int clamped, double *out);
+int smx_spectral_contrast_of_spectrogram_dev_f32(const float *d_s, int64_t lead, int64_t bins, int64_t frames,
+                                                 int64_t fft_size, int64_t n_bands, double f_min, double quantile,
+                                                 int linear, int64_t sample_rate, int clamped, float *d_out, void *stream);
+int smx_onset_strength_f32(const smx_stft_config *sc, const smx_mel_config *mc, const float *x, int64_t lead, int64_t n,
+                           int64_t lag, float *out);
+int smx_onset_strength_f64(const smx_stft_config *sc, const smx_mel_config *mc, const double *x, int64_t lead, int64_t n,
+                           int64_t lag, double *out);
+int smx_onset_strength_dev_f32(const smx_stft_config *sc, const smx_mel_config *mc, const float *d_x, int64_t lead,
+                               int64_t n, int64_t x_stride, int64_t lag, float *d_out, void *stream);
+int smx_onset_flux_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, int64_t lag, float *out);
+int smx_onset_flux_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, int64_t lag, double *out);
+int smx_onset_flux_dev_f32(const float *d_s, int64_t lead, int64_t bins, int64_t frames, int64_t lag, float *d_out,
+                           void *stream);
+
 /* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
  * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
  * independent planes):

@@ -24,6 +24,8 @@ from . import convert as Convert
 from .features import mel_spectrogram, mfcc, chroma_stft, chroma_cqt, power_to_db, amplitude_to_db
 from .spectral import (spectral_centroid, spectral_bandwidth, spectral_rolloff, spectral_flatness,
                        spectral_centroid_stage, spectral_bandwidth_stage, spectral_rolloff_stage, spectral_flatness_stage)
+from .contrast import spectral_contrast, spectral_contrast_of_spectrogram, spectral_contrast_stage
+from .onset import onset_strength, onset_strength_stage
 from . import hpss as Hpss
 from .hpss import hpss_masks, hpss_of_spectrogram, hpss_of_stft, hpss, harmonic, percussive
 from . import effects as Effects
@@ -71,5 +73,5 @@ def get_devices():
 
 
 __all__ = ["Stft", "Mel", "Chroma", "Cqt", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "chroma_cqt", "power_to_db", "amplitude_to_db", "spectral_centroid",
-           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
+           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_contrast_of_spectrogram", "spectral_contrast_stage", "onset_strength", "onset_strength_stage", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

@@ -119,6 +119,19 @@ SIGNATURES = {
     "smx_spectral_flatness_f32": (cint, [vp, i64, i64, i64, f64, f64, vp]),
     "smx_spectral_flatness_f64": (cint, [vp, i64, i64, i64, f64, f64, vp]),
     "smx_spectral_flatness_f32_dev": (cint, [vp, i64, i64, i64, f64, f64, vp, vp]),
+    "smx_spectral_contrast_plan": (cint, [i64, f64, f64, i64, i64, vp, vp, vp]),
+    "smx_spectral_contrast_f32": (cint, [vp, vp, i64, i64, i64, f64, f64, cint, i64, vp]),
+    "smx_spectral_contrast_f64": (cint, [vp, vp, i64, i64, i64, f64, f64, cint, i64, vp]),
+    "smx_spectral_contrast_dev_f32": (cint, [vp, vp, i64, i64, i64, i64, f64, f64, cint, i64, vp, vp]),
+    "smx_spectral_contrast_of_spectrogram_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, cint, i64, cint, vp]),
+    "smx_spectral_contrast_of_spectrogram_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, cint, i64, cint, vp]),
+    "smx_spectral_contrast_of_spectrogram_dev_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, cint, i64, cint, vp, vp]),
+    "smx_onset_strength_f32": (cint, [vp, vp, vp, i64, i64, i64, vp]),
+    "smx_onset_strength_f64": (cint, [vp, vp, vp, i64, i64, i64, vp]),
+    "smx_onset_strength_dev_f32": (cint, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
+    "smx_onset_flux_f32": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_onset_flux_f64": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_onset_flux_dev_f32": (cint, [vp, i64, i64, i64, i64, vp, vp]),
     "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
