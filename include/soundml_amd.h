@@ -461,6 +461,53 @@ int smx_onset_flux_f64(const double *s, int64_t lead, int64_t bins, int64_t fram
 int smx_onset_flux_dev_f32(const float *d_s, int64_t lead, int64_t bins, int64_t frames, int64_t lag, float *d_out,
                            void *stream);
 
+/* ---- Energy (energy.ml; Soundml.rms, rms_of_spectrogram, zero_crossing_rate and the two stages) ----------------------
+ * Frame features of audio x [lead; n] -> [lead; frames].  The grid (energy.ml:107-118): border = frame_length / 2,
+ * frames = 0 for n = 0, else 1 + (n + 2 border - frame_length) / hop; frame p covers padded positions
+ * [p hop, p hop + frame_length).  hop > frame_length, odd frame lengths, frame_length 1 and n < border are legal.
+ *   rms                  energy.ml:126-129, 380-381: zero borders, sqrt(sum x^2 / frame_length) in float64, one rounding
+ *   zero_crossing_rate   energy.ml:136-148, 383-388: borders copy the first / last sample; a sample is negative iff
+ *                        (double)x < -threshold (NaN is not); a crossing is a change of that flag between positions
+ *                        j - 1 and j of the frame, j = 1 .. frame_length - 1; count / frame_length, one rounding
+ *   rms_of_spectrogram   energy.ml:394-421: magnitudes s [lead; bins; frames] -> [lead; frames], bins = frame_length / 2 + 1:
+ *                        sqrt(2 sum_k w_k s_k^2 / frame_length^2), w = 0.5 at bin 0 and (even frame_length) at the last
+ *                        bin, bins walked in ascending order; no sign check
+ *   energy_frames        the stages' body (energy.ml:157-183): frames [0, count) of a segment x [lead; n] of the padded
+ *                        stream, no border; (count - 1) hop + frame_length <= n.  op 0: rms, 1: zero-crossing rate
+ *                        (threshold is read by op 1 only).  Errors are worded for rms_stage / zero_crossing_rate_stage.
+ * A frame's float64 sum of squares has ONE order, a function of its own samples: blocks of
+ * min(hop, frame_length) samples from the frame's start; in a block lane l of 64 adds elements l, l + 64, ... in ascending
+ * order and the lane sums meet in the butterfly of xor distances 32, 16, 8, 4, 2, 1; the blocks' partials are added in
+ * ascending order.  A batch slice, any chunking of the stages and both kernels (SMX_DISABLE_FAST) give the same bits.
+ * Checks, in the reference's order and words (energy.ml:78-105, 394-408): the flat faces threshold, frame_length, hop; the
+ * stages' body frame_length, hop, threshold; rms_of_spectrogram frame_length, then bins.  Zero-size axes write nothing.
+ *
+ * The device-resident forms end in `_device_f32`: both placement suites keep closed tables of the names that end in the
+ * shorter word, before or behind the dtype; these have a table and a law of their own (tests/test_gpu_placement_energy.py).
+ * They take rows x_stride >= n apart and enqueue on `stream`; nothing synchronises it. */
+int smx_rms_f32(const float *x, int64_t lead, int64_t n, int64_t frame_length, int64_t hop, float *out);
+int smx_rms_f64(const double *x, int64_t lead, int64_t n, int64_t frame_length, int64_t hop, double *out);
+int smx_rms_device_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t frame_length, int64_t hop,
+                       float *d_out, void *stream);
+int smx_zero_crossing_rate_f32(const float *x, int64_t lead, int64_t n, int64_t frame_length, int64_t hop,
+                               double threshold, float *out);
+int smx_zero_crossing_rate_f64(const double *x, int64_t lead, int64_t n, int64_t frame_length, int64_t hop,
+                               double threshold, double *out);
+int smx_zero_crossing_rate_device_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t frame_length,
+                                      int64_t hop, double threshold, float *d_out, void *stream);
+int smx_rms_of_spectrogram_f32(const float *s, int64_t lead, int64_t bins, int64_t frames, int64_t frame_length,
+                               float *out);
+int smx_rms_of_spectrogram_f64(const double *s, int64_t lead, int64_t bins, int64_t frames, int64_t frame_length,
+                               double *out);
+int smx_rms_of_spectrogram_device_f32(const float *d_s, int64_t lead, int64_t bins, int64_t frames, int64_t frame_length,
+                                      float *d_out, void *stream);
+int smx_energy_frames_f32(int op, double threshold, int64_t frame_length, int64_t hop, const float *x, int64_t lead,
+                          int64_t n, int64_t count, float *out);
+int smx_energy_frames_f64(int op, double threshold, int64_t frame_length, int64_t hop, const double *x, int64_t lead,
+                          int64_t n, int64_t count, double *out);
+int smx_energy_frames_device_f32(int op, double threshold, int64_t frame_length, int64_t hop, const float *d_x,
+                                 int64_t lead, int64_t n, int64_t x_stride, int64_t count, float *d_out, void *stream);
+
 /* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
  * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
  * independent planes):

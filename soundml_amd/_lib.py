@@ -132,6 +132,18 @@ SIGNATURES = {
     "smx_onset_flux_f32": (cint, [vp, i64, i64, i64, i64, vp]),
     "smx_onset_flux_f64": (cint, [vp, i64, i64, i64, i64, vp]),
     "smx_onset_flux_dev_f32": (cint, [vp, i64, i64, i64, i64, vp, vp]),
+    "smx_rms_f32": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_rms_f64": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_rms_device_f32": (cint, [vp, i64, i64, i64, i64, i64, vp, vp]),
+    "smx_zero_crossing_rate_f32": (cint, [vp, i64, i64, i64, i64, f64, vp]),
+    "smx_zero_crossing_rate_f64": (cint, [vp, i64, i64, i64, i64, f64, vp]),
+    "smx_zero_crossing_rate_device_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, vp, vp]),
+    "smx_rms_of_spectrogram_f32": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_rms_of_spectrogram_f64": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_rms_of_spectrogram_device_f32": (cint, [vp, i64, i64, i64, i64, vp, vp]),
+    "smx_energy_frames_f32": (cint, [cint, f64, i64, i64, vp, i64, i64, i64, vp]),
+    "smx_energy_frames_f64": (cint, [cint, f64, i64, i64, vp, i64, i64, i64, vp]),
+    "smx_energy_frames_device_f32": (cint, [cint, f64, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
     "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
