@@ -349,6 +349,54 @@ int smx_amplitude_to_db_f64(const double *s, int64_t total, double reference, do
 int smx_amplitude_to_db_f32_dev(const float *d_s, int64_t total, double reference, double amin, int has_top_db,
                                 double top_db, float *d_out, void *stream);
 
+/* ---- Convert.db_to_power / db_to_amplitude (convert.ml:58-68): reference * 10^(db / 10) and reference * 10^(db / 20),
+ * evaluated in float64 and rounded once to the data's dtype.  `total` elements of any shape; out may alias db on the
+ * device.  Invalid_argument (convert.ml:3-6): reference not finite and positive.                                 */
+int smx_db_to_power_f32(const float *db, int64_t total, double reference, float *out);
+int smx_db_to_power_f64(const double *db, int64_t total, double reference, double *out);
+int smx_db_to_power_f32_dev(const float *d_db, int64_t total, double reference, float *d_out, void *stream);
+int smx_db_to_power_f64_dev(const double *d_db, int64_t total, double reference, double *d_out, void *stream);
+int smx_db_to_amplitude_f32(const float *db, int64_t total, double reference, float *out);
+int smx_db_to_amplitude_f64(const double *db, int64_t total, double reference, double *out);
+int smx_db_to_amplitude_f32_dev(const float *d_db, int64_t total, double reference, float *d_out, void *stream);
+int smx_db_to_amplitude_f64_dev(const double *d_db, int64_t total, double reference, double *d_out, void *stream);
+/* Convert.hz_to_midi / midi_to_hz (convert.ml:104-106): 12 log2 (f / 440) + 69 and back; host float64 */
+int smx_hz_to_midi(const double *f, int64_t n, double *out);
+int smx_midi_to_hz(const double *m, int64_t n, double *out);
+/* Convert.frames_to_time / time_to_frames (convert.ml:108-115): frames * hop / sample_rate, and floor (times *
+ * sample_rate / hop); host float64.  Invalid_argument (convert.ml:18-20): sample_rate < 1, hop < 1.           */
+int smx_frames_to_time(int64_t sample_rate, int64_t hop, const double *frames, int64_t n, double *out);
+int smx_time_to_frames(int64_t sample_rate, int64_t hop, const double *times, int64_t n, double *out);
+
+/* ---- Mel.invert (DESIGN.md "Mel inversion"): m [lead; n_mels; frames] -> out [lead; bins; frames], per frame the
+ * non-negative s that approaches min |W s - m|_2 after n_iter rounds of accelerated projected gradient from zero, in
+ * the data's dtype, all rounds inside one launch.  power = 1: s itself; otherwise s^(1 / power) in float64 rounded once
+ * (mel_to_stft: the magnitudes behind a spectrogram raised to `power`; power 2 is a square root).
+ * Invalid_argument: a handle of smx_mel_config_from_weights, n_mels != the config's, n_iter < 0, power not finite and
+ * positive.                                                                                                     */
+int smx_mel_invert_f32(const smx_mel_config *c, const float *m, int64_t lead, int64_t n_mels, int64_t frames,
+                       int64_t n_iter, double power, float *out);
+int smx_mel_invert_f64(const smx_mel_config *c, const double *m, int64_t lead, int64_t n_mels, int64_t frames,
+                       int64_t n_iter, double power, double *out);
+int smx_mel_invert_f32_dev(const smx_mel_config *c, const float *d_m, int64_t lead, int64_t n_mels, int64_t frames,
+                           int64_t n_iter, double power, float *d_out, void *stream);
+int smx_mel_invert_f64_dev(const smx_mel_config *c, const double *d_m, int64_t lead, int64_t n_mels, int64_t frames,
+                           int64_t n_iter, double power, double *d_out, void *stream);
+
+/* ---- mfcc_to_mel: the tail of Soundml.mfcc backwards (soundml.ml:26-95; DESIGN.md "Mel inversion"): row k divided by
+ * its lifter weight 1 + (lifter / 2) sin (pi (k + 1) / lifter), the cepstral axis zero-padded to n_mels, the inverse of
+ * the orthonormal DCT-II along it, then reference * 10^(db / 10); float64 inside, one rounding.
+ * c [lead; n_mfcc; frames] -> out [lead; n_mels; frames].  Invalid_argument: n_mels < n_mfcc, n_mfcc < 1, lifter
+ * negative or not finite, a lifter weight of exactly zero, reference not finite and positive.                   */
+int smx_mfcc_to_mel_f32(const float *c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter,
+                        double lifter, double reference, float *out);
+int smx_mfcc_to_mel_f64(const double *c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter,
+                        double lifter, double reference, double *out);
+int smx_mfcc_to_mel_f32_dev(const float *d_c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels,
+                            int has_lifter, double lifter, double reference, float *d_out, void *stream);
+int smx_mfcc_to_mel_f64_dev(const double *d_c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels,
+                            int has_lifter, double lifter, double reference, double *d_out, void *stream);
+
 /* ---- Soundml.mfcc (soundml.ml:50-95): mel_spectrogram (power 2) -> power_to_db with the 80 dB clamp under
  * the maximum of the WHOLE tensor (convert.ml:30-50) -> orthonormal DCT-II along the mel axis, first n_mfcc
  * rows -> optional sinusoidal lifter.  float64 interior after the mel spectrogram, one rounding to the audio

@@ -230,6 +230,26 @@ SIGNATURES = {
     "smx_amplitude_to_db_f32": (cint, [vp, i64, f64, f64, cint, f64, vp]),
     "smx_amplitude_to_db_f64": (cint, [vp, i64, f64, f64, cint, f64, vp]),
     "smx_amplitude_to_db_f32_dev": (cint, [vp, i64, f64, f64, cint, f64, vp, vp]),
+    "smx_db_to_power_f32": (cint, [vp, i64, f64, vp]),
+    "smx_db_to_power_f64": (cint, [vp, i64, f64, vp]),
+    "smx_db_to_power_f32_dev": (cint, [vp, i64, f64, vp, vp]),
+    "smx_db_to_power_f64_dev": (cint, [vp, i64, f64, vp, vp]),
+    "smx_db_to_amplitude_f32": (cint, [vp, i64, f64, vp]),
+    "smx_db_to_amplitude_f64": (cint, [vp, i64, f64, vp]),
+    "smx_db_to_amplitude_f32_dev": (cint, [vp, i64, f64, vp, vp]),
+    "smx_db_to_amplitude_f64_dev": (cint, [vp, i64, f64, vp, vp]),
+    "smx_hz_to_midi": (cint, [vp, i64, vp]),
+    "smx_midi_to_hz": (cint, [vp, i64, vp]),
+    "smx_frames_to_time": (cint, [i64, i64, vp, i64, vp]),
+    "smx_time_to_frames": (cint, [i64, i64, vp, i64, vp]),
+    "smx_mel_invert_f32": (cint, [vp, vp, i64, i64, i64, i64, f64, vp]),
+    "smx_mel_invert_f64": (cint, [vp, vp, i64, i64, i64, i64, f64, vp]),
+    "smx_mel_invert_f32_dev": (cint, [vp, vp, i64, i64, i64, i64, f64, vp, vp]),
+    "smx_mel_invert_f64_dev": (cint, [vp, vp, i64, i64, i64, i64, f64, vp, vp]),
+    "smx_mfcc_to_mel_f32": (cint, [vp, i64, i64, i64, i64, cint, f64, f64, vp]),
+    "smx_mfcc_to_mel_f64": (cint, [vp, i64, i64, i64, i64, cint, f64, f64, vp]),
+    "smx_mfcc_to_mel_f32_dev": (cint, [vp, i64, i64, i64, i64, cint, f64, f64, vp, vp]),
+    "smx_mfcc_to_mel_f64_dev": (cint, [vp, i64, i64, i64, i64, cint, f64, f64, vp, vp]),
     "smx_window_make_param": (cint, [cint, f64, cint, i64, vp]),
     "smx_window_cola": (cint, [cint, f64, i64, i64, C.POINTER(cint)]),
     "smx_hz_to_mel": (cint, [cint, vp, i64, vp]),

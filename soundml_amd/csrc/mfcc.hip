@@ -438,6 +438,59 @@ void launch_mfcc(const MfccJob &job) {
   SMX_HIP_CHECK(hipFreeAsync(d_max, job.stream));
 }
 
+namespace {
+// The tail backwards (mfcc_to_mel): v_k = c_k / lifter_k * scale_k, db_m = sum_k v_k * 2 cos (pi k (2 m + 1) / (2 n_mels)) over the
+// n_mfcc rows that exist (the padded ones are zero) in ascending k -- the transpose of the orthonormal DCT-II is its inverse --,
+// mel_m = reference * 10^(db_m / 10); float64 inside, one rounding.  One thread per (clip, frame), frames across lanes; the
+// coefficients stay in registers for the usual counts, the DCT rows come as wave-uniform loads.
+template <typename T, int NC>
+__global__ void __launch_bounds__(256) mfcc_to_mel_kernel(MfccArgs a, double reference) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t clip = blockIdx.y;
+  if (t >= a.frames) return;
+  const T *c = reinterpret_cast<const T *>(a.mel) + clip * a.n_mfcc * a.frames + t;   // (the job's input: cepstra)
+  T *out = reinterpret_cast<T *>(a.out) + clip * a.n_mels * a.frames + t;
+  auto coefficient = [&](int k) { return (double)c[(int64_t)k * a.frames] / a.post[2 * k + 1] * a.post[2 * k]; };
+  double v[NC > 0 ? NC : 1];
+  if (NC > 0) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) v[k] = k < a.n_mfcc ? coefficient(k) : 0.0;
+  }
+  for (int m = 0; m < a.n_mels; ++m) {
+    double db = 0.0;
+    if (NC > 0) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k)
+        if (k < a.n_mfcc) db = fma(v[k], a.dct[(int64_t)k * a.n_mels + m], db);
+    } else {
+      for (int k = 0; k < a.n_mfcc; ++k) db = fma(coefficient(k), a.dct[(int64_t)k * a.n_mels + m], db);
+    }
+    out[(int64_t)m * a.frames] = (T)(reference * pow(10.0, db / 10.0));
+  }
+}
+}  // namespace
+
+void launch_mfcc_to_mel(const MfccToMelJob &job) {
+  if (job.lead <= 0 || job.frames <= 0) return;
+  if (job.lead > 65535) throw Failure("mfcc_to_mel: too many leading slices for one launch");
+  const double *d_tab = mfcc_tables(job.n_mels, job.n_mfcc, job.lifter);
+  MfccArgs a{};
+  a.mel = job.c;
+  a.out = job.out;
+  a.dct = d_tab;
+  a.post = d_tab + (size_t)job.n_mfcc * job.n_mels;
+  a.lead = job.lead;
+  a.frames = job.frames;
+  a.n_mels = job.n_mels;
+  a.n_mfcc = job.n_mfcc;
+  dim3 grid((unsigned)((job.frames + 255) / 256), (unsigned)job.lead);
+  auto go = [&](auto kernel) { SMX_LAUNCH(kernel, grid, dim3(256), 0, job.stream, a, job.reference); };
+  const bool wide = job.elem_bytes == 8;
+  if (job.n_mfcc <= 32) wide ? go(mfcc_to_mel_kernel<double, 32>) : go(mfcc_to_mel_kernel<float, 32>);
+  else wide ? go(mfcc_to_mel_kernel<double, 0>) : go(mfcc_to_mel_kernel<float, 0>);
+  SMX_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace smx
 
 // ---- the C ABI's side: Soundml.mfcc, Convert.power_to_db / amplitude_to_db -------------------------------------------------
@@ -495,6 +548,59 @@ void mfcc_host(const smx_stft_config &sc, const smx_mel_config &mc, const void *
   host_call("mfcc", {{x, (size_t)n * (size_t)in_bytes}}, out, (size_t)n_mfcc * (size_t)count * (size_t)in_bytes, lead, false, nullptr,
             [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
               mfcc_dev(sc, mc, d_in[0], in_bytes, nc, n, n, n_mfcc, has_lifter, lifter, d_out, stream);
+            });
+}
+
+// ---- mfcc_to_mel: the tail of Soundml.mfcc backwards (soundml.ml:26-95) --------------------------------------
+void check_mfcc_to_mel(int64_t n_mfcc, int64_t n_mels, int has_lifter, double lifter, double reference) {
+  if (n_mfcc < 1 || n_mels < n_mfcc || n_mels > 0x7fffffff)
+    throw InvalidArgument(format(
+        "mfcc_to_mel: cannot spread %lld cepstral coefficients over %lld mel bands (n_mels must be at least n_mfcc, and n_mfcc at least 1)",
+        (long long)n_mfcc, (long long)n_mels));
+  if (has_lifter && !(std::isfinite(lifter) && lifter >= 0.0))
+    throw InvalidArgument(format("mfcc_to_mel: cannot undo a lifter with a coefficient of %g (lifter must be finite and non-negative)",
+                                 lifter));
+  if (has_lifter && lifter > 0.0) {
+    const double pi = 3.14159265358979323846;
+    for (int64_t k = 0; k < n_mfcc; ++k)
+      if (1.0 + lifter / 2.0 * std::sin(pi * (double)(k + 1) / lifter) == 0.0)
+        throw InvalidArgument(format("mfcc_to_mel: cannot undo a lifter of %g (its weight for coefficient %lld is zero)", lifter,
+                                     (long long)k));
+  }
+  if (!(std::isfinite(reference) && reference > 0.0))
+    throw InvalidArgument("Soundml.Convert.db_to_power: reference must be finite and positive");
+}
+
+void mfcc_to_mel_dev(const void *d_c, int elem_bytes, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter,
+                     double lifter, double reference, void *d_out, hipStream_t stream) {
+  check_mfcc_to_mel(n_mfcc, n_mels, has_lifter, lifter, reference);
+  if (lead < 0 || frames < 0) throw Failure("mfcc_to_mel: negative extent");
+  if (lead == 0 || frames == 0) return;
+  if (!d_c || !d_out) throw Failure("mfcc_to_mel: null device pointer");
+  MfccToMelJob job;
+  job.c = d_c;
+  job.elem_bytes = elem_bytes;
+  job.lead = lead;
+  job.frames = frames;
+  job.n_mels = (int)n_mels;
+  job.n_mfcc = (int)n_mfcc;
+  job.lifter = has_lifter ? lifter : 0.0;
+  job.reference = reference;
+  job.out = d_out;
+  job.stream = stream;
+  launch_mfcc_to_mel(job);
+}
+
+void mfcc_to_mel_host(const void *c, int elem_bytes, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter,
+                      double lifter, double reference, void *out) {
+  check_mfcc_to_mel(n_mfcc, n_mels, has_lifter, lifter, reference);
+  if (lead < 0 || frames < 0) throw Failure("mfcc_to_mel: negative extent");
+  if (lead == 0 || frames == 0) return;
+  if (!c || !out) throw Failure("mfcc_to_mel: null pointer");
+  host_call("mfcc_to_mel", {{c, (size_t)n_mfcc * (size_t)frames * (size_t)elem_bytes}}, out,
+            (size_t)n_mels * (size_t)frames * (size_t)elem_bytes, lead, false, nullptr,
+            [&](const void *const *d_in, void *d_out, int64_t nc, hipStream_t stream) {
+              mfcc_to_mel_dev(d_in[0], elem_bytes, nc, n_mfcc, frames, n_mels, has_lifter, lifter, reference, d_out, stream);
             });
 }
 
@@ -573,6 +679,28 @@ int smx_amplitude_to_db_f64(const double *s, int64_t total, double reference, do
 int smx_amplitude_to_db_f32_dev(const float *d_s, int64_t total, double reference, double amin, int has_top_db, double top_db,
                                 float *d_out, void *stream) {
   return guarded([&] { to_db_dev(true, d_s, 4, total, reference, amin, has_top_db, top_db, d_out, (hipStream_t)stream); });
+}
+
+// ---- mfcc_to_mel -----------------------------------------------------------------------------------
+int smx_mfcc_to_mel_f32(const float *c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter, double lifter,
+                        double reference, float *out) {
+  return guarded([&] { mfcc_to_mel_host(c, 4, lead, n_mfcc, frames, n_mels, has_lifter, lifter, reference, out); });
+}
+int smx_mfcc_to_mel_f64(const double *c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter, double lifter,
+                        double reference, double *out) {
+  return guarded([&] { mfcc_to_mel_host(c, 8, lead, n_mfcc, frames, n_mels, has_lifter, lifter, reference, out); });
+}
+int smx_mfcc_to_mel_f32_dev(const float *d_c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter,
+                            double lifter, double reference, float *d_out, void *stream) {
+  return guarded([&] {
+    mfcc_to_mel_dev(d_c, 4, lead, n_mfcc, frames, n_mels, has_lifter, lifter, reference, d_out, (hipStream_t)stream);
+  });
+}
+int smx_mfcc_to_mel_f64_dev(const double *d_c, int64_t lead, int64_t n_mfcc, int64_t frames, int64_t n_mels, int has_lifter,
+                            double lifter, double reference, double *d_out, void *stream) {
+  return guarded([&] {
+    mfcc_to_mel_dev(d_c, 8, lead, n_mfcc, frames, n_mels, has_lifter, lifter, reference, d_out, (hipStream_t)stream);
+  });
 }
 
 // ---- Soundml.mfcc (soundml.ml:50-95) --------------------------------------------------------------

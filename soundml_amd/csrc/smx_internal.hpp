@@ -185,6 +185,17 @@ struct MelFusedPlan {      // per device; built lazily by stft_fast.hip
   int state = 0;           // 0 not built, 1 usable, -1 this configuration is not eligible
   int resident = 0;        // fused4 plans: w_mfma is [wave][64 steps][64 lanes], a wave's items in order (the kernel keeps them in registers)
 };
+// Mel.invert's tables (mel_invert.hip; DESIGN.md "Mel inversion"), per device and element width, one allocation: the weights
+// rounded to the data's dtype row by row over each band, the rows dealt to lanes, and per bin its at most two rows
+struct MelInvertPlan {
+  void *buf = nullptr;      // the one device allocation behind the pointers below
+  const void *w_rows = nullptr;   // T [nnz]: the band weights of the row in slot i of lane l at offset + 64 q, ascending bins q
+  const int4 *rows = nullptr;     // [slots * 64] {row (-1: none), band_lo, band length, offset}: slot i of lane l at i * 64 + l
+  const void *bins = nullptr;     // per bin {T w0, w1; int j0, j1}: the rows that touch it (j1 = -1: one row; j0 = -1: none)
+  int slots = 0;            // rows per lane
+  int64_t nnz = 0;          // entries of w_rows (64 x the slots' longest bands)
+  double lipschitz = 0.0;   // max_j sum_i |(W W^T)_ji| over the float64 weights
+};
 }  // namespace smx
 
 struct smx_mel_config {
@@ -209,12 +220,14 @@ struct smx_mel_config {
   const Tables &tables() const;
   const smx::MelFusedPlan &fused32_plan() const; // stft_fast.hip: items of the 32-lane mel kernel (items = Mel32Item[8][8])
   const smx::MelFusedPlan &fused4_plan() const;  // stft_fast.hip: the same product on 4 x 4 x 1 blocks (items = Mel4Item[8][8]; fft 2048)
+  const smx::MelInvertPlan &invert_plan(int elem_bytes) const;   // mel_invert.hip
   ~smx_mel_config();
 
  private:
   mutable std::mutex mutex_;
   mutable std::map<int, Tables> tables_;
   mutable std::map<int, smx::MelFusedPlan> fused32_, fused4_;
+  mutable std::map<std::pair<int, int>, smx::MelInvertPlan> invert_;   // (device, element bytes)
 };
 
 // Chroma.Config.t (chroma.ml:95-107): the [n_chroma; bins] projection matrix, float64, built once on the host
@@ -465,6 +478,43 @@ struct ToDbJob {
   hipStream_t stream = nullptr;
 };
 void launch_to_db(const ToDbJob &job);            // mfcc.hip
+
+// Convert.db_to_power / db_to_amplitude (convert.ml:58-68): reference * 10^(db / gain) in float64, one rounding
+struct FromDbJob {
+  const void *db = nullptr;
+  void *out = nullptr;           // same shape and dtype; may alias db
+  int elem_bytes = 4;
+  int64_t total = 0;
+  double gain = 10.0, reference = 1.0;
+  hipStream_t stream = nullptr;
+};
+void launch_from_db(const FromDbJob &job);        // convert.hip
+
+// Mel.invert (DESIGN.md "Mel inversion"): per frame the non-negative s that approaches min |W s - m|, n_iter accelerated
+// projected-gradient rounds inside one launch; root != 1: s^(1 / root) stored instead (mel_to_stft)
+struct MelInvertJob {
+  const smx_mel_config *cfg = nullptr;
+  const void *m = nullptr;       // device [lead; n_mels; frames]
+  int elem_bytes = 4;
+  int64_t lead = 0, frames = 0, n_iter = 0;
+  double root = 1.0;
+  void *out = nullptr;           // device [lead; bins; frames]
+  hipStream_t stream = nullptr;
+};
+void launch_mel_invert(const MelInvertJob &job);  // mel_invert.hip
+
+// the inverse of Soundml.mfcc's tail (soundml.ml:26-95): un-lifter, zero-pad, inverse orthonormal DCT-II, db_to_power
+struct MfccToMelJob {
+  const void *c = nullptr;       // device [lead; n_mfcc; frames]
+  int elem_bytes = 4;
+  int64_t lead = 0, frames = 0;
+  int n_mels = 0, n_mfcc = 0;
+  double lifter = 0.0;           // 0: none
+  double reference = 1.0;
+  void *out = nullptr;           // device [lead; n_mels; frames]
+  hipStream_t stream = nullptr;
+};
+void launch_mfcc_to_mel(const MfccToMelJob &job); // mfcc.hip
 
 // spectral-shape features over a device-resident spectrogram [lead; bins; frames] (spectral.ml:171-255)
 enum SpectralFeature { SPECTRAL_CENTROID = 0, SPECTRAL_BANDWIDTH = 1, SPECTRAL_ROLLOFF = 2, SPECTRAL_FLATNESS = 3 };

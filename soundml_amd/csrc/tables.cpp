@@ -452,6 +452,7 @@ smx_mel_config::~smx_mel_config() {
     (void)hipFree(kv.second.block_hi);
     (void)hipFree(kv.second.tile_hi);
   }
+  for (auto &kv : invert_) (void)hipFree(kv.second.buf);
   for (auto &kv : fused32_) {
     (void)hipFree(kv.second.items);
     (void)hipFree(kv.second.w_mfma);

@@ -93,6 +93,34 @@ def apply(c: Config, s):
     return b.wrap(out)
 
 
+def _invert(c: Config, m, n_iter, power):
+    nd = len(m.shape)
+    if nd < 2:
+        raise _lib.InvalidArgument(
+            "invert: cannot invert a rank-%d tensor (the mel inversion needs [...; n_mels; frames])" % nd)
+    b = Batch(m, "invert")
+    lead_shape = b.shape[:-2]
+    n_mels, frames = int(b.shape[-2]), int(b.shape[-1])
+    lead = prod(lead_shape)
+    sfx = "f32" if b.bytes == 4 else "f64"
+    args = (lead, n_mels, frames, int(n_iter), float(power))
+    check(getattr(lib, "smx_mel_invert_%s" % sfx)(c._h, None, 0, n_mels, 0, int(n_iter), float(power), None))   # the checks first
+    out = b.empty(lead_shape + (c.bins, frames))
+    if b.device:
+        with b.device_guard():
+            check(getattr(lib, "smx_mel_invert_%s_dev" % sfx)(c._h, b.ptr(), *args, out_ptr(out), b.stream()))
+        return out
+    check(getattr(lib, "smx_mel_invert_%s" % sfx)(c._h, b.ptr(), *args, out_ptr(out)))
+    return b.wrap(out)
+
+
+def invert(c: Config, m, n_iter: int = 200):
+    """``Mel.invert c m``: [...; n_mels; frames] -> [...; bins; frames], per frame the non-negative spectrum s that
+    approaches min |W s - m| after ``n_iter`` rounds of accelerated projected gradient from zero, in m's dtype
+    (DESIGN.md "Mel inversion").  Only for configs of ``Config.create``."""
+    return _invert(c, m, n_iter, 1.0)
+
+
 def stage(c: Config):
     """``Mel.stage c`` (mel.ml:233): ``apply c`` as a memoryless Pipeline stage."""
     from ._tensor import Stateless
