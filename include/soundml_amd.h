@@ -556,6 +556,53 @@ int smx_energy_frames_f64(int op, double threshold, int64_t frame_length, int64_
 int smx_energy_frames_device_f32(int op, double threshold, int64_t frame_length, int64_t hop, const float *d_x,
                                  int64_t lead, int64_t n, int64_t x_stride, int64_t count, float *d_out, void *stream);
 
+/* ---- Pitch: YIN fundamental-frequency tracking (de Cheveigne & Kawahara 2002; not in the reference) ------------------------
+ * Audio x [lead; n] -> f0 and aperiodicity [lead; frames], or the normalised difference d' [lead; pmax + 1; frames].  The grid
+ * is that of rms: border = frame_length / 2 virtual zeros on each side, frames = 0 for n = 0, else
+ * 1 + (n + 2 border - frame_length) / hop; frame p covers padded positions [p hop, p hop + frame_length).
+ * Per frame, samples x_0 .., W = frame_length / 2, pmin = floor(sample_rate / fmax),
+ * pmax = min(ceil(sample_rate / fmin), frame_length - W - 1), all in float64, one rounding into the dtype of the input:
+ *   r(tau) = sum_{j < W} x_j x_{j + tau};  P(i) = sum_{j < i} x_j^2;  e(tau) = P(tau + W) - P(tau)
+ *   d(tau) = max(0, (e(0) + e(tau)) - 2 r(tau)), a NaN staying one;  c(tau) = d(1) + .. + d(tau);  d'(0) = 1, d'(tau) = (d(tau) tau) / c(tau),
+ *   1 where c(tau) = 0
+ *   the lag: the smallest tau in [pmin, pmax] with d'(tau) < trough_threshold, d'(tau) <= d'(tau - 1) and (tau = pmax or
+ *   d'(tau) < d'(tau + 1)); if none, the smallest tau of the range that attains the minimum of d'
+ *   the shift: with a, b, c = d'(tau - 1), d'(tau), d'(tau + 1) where tau + 1 <= pmax, den = (a - 2 b) + c:
+ *   (0.5 (a - c)) / den if den > 0 and its magnitude is at most 1, else 0
+ *   f0 = sample_rate / (tau + shift), aperiodicity = d'(tau); both NaN where e(0) or c(pmax) is not finite
+ * The sums have ONE order, a function of the frame's own samples: j < W in blocks of min(hop, W) from the
+ * frame's start, a block's partial one ascending chain from 0.0, the partials added in ascending order; P one ascending
+ * chain from the frame's first sample.  Float32 samples: fma (the products are exact); float64: product and sum round in turn.
+ * A batch slice, a frame range, any chunking of the stage and both kernels (SMX_DISABLE_FAST) give the same bits.
+ *   yin_frames   the stage's body: frames [0, count) of a segment x [lead; n] of the padded stream, no border;
+ *                (count - 1) hop + frame_length <= n.  Errors are worded for yin_stage.
+ * Checks, in this order: sample_rate >= 1, frame_length >= 4, hop >= 1, fmin and fmax finite with
+ * 0 < fmin < fmax <= sample_rate / 2, trough_threshold finite and positive (not read by yin_difference), pmax > pmin.
+ * aperiodicity may be NULL.  Zero-size axes write nothing; a call with null data and zero extents checks the parameters only.
+ *
+ * The device-resident forms end in `_resident_f32` (tests/test_gpu_placement_pitch.py keeps their table and law): rows
+ * x_stride >= n apart, enqueued on `stream`, nothing synchronises it and no flag is read back. */
+int smx_yin_f32(const float *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax, int64_t frame_length,
+                int64_t hop, double trough_threshold, float *f0, float *aperiodicity);
+int smx_yin_f64(const double *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax, int64_t frame_length,
+                int64_t hop, double trough_threshold, double *f0, double *aperiodicity);
+int smx_yin_resident_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t sample_rate, double fmin,
+                         double fmax, int64_t frame_length, int64_t hop, double trough_threshold, float *d_f0,
+                         float *d_aperiodicity, void *stream);
+int smx_yin_difference_f32(const float *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax,
+                           int64_t frame_length, int64_t hop, float *out);
+int smx_yin_difference_f64(const double *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax,
+                           int64_t frame_length, int64_t hop, double *out);
+int smx_yin_difference_resident_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t sample_rate,
+                                    double fmin, double fmax, int64_t frame_length, int64_t hop, float *d_out, void *stream);
+int smx_yin_frames_f32(const float *x, int64_t lead, int64_t n, int64_t count, int64_t sample_rate, double fmin, double fmax,
+                       int64_t frame_length, int64_t hop, double trough_threshold, float *f0, float *aperiodicity);
+int smx_yin_frames_f64(const double *x, int64_t lead, int64_t n, int64_t count, int64_t sample_rate, double fmin, double fmax,
+                       int64_t frame_length, int64_t hop, double trough_threshold, double *f0, double *aperiodicity);
+int smx_yin_frames_resident_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t count, int64_t sample_rate,
+                                double fmin, double fmax, int64_t frame_length, int64_t hop, double trough_threshold,
+                                float *d_f0, float *d_aperiodicity, void *stream);
+
 /* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
  * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
  * independent planes):

@@ -144,6 +144,15 @@ SIGNATURES = {
     "smx_energy_frames_f32": (cint, [cint, f64, i64, i64, vp, i64, i64, i64, vp]),
     "smx_energy_frames_f64": (cint, [cint, f64, i64, i64, vp, i64, i64, i64, vp]),
     "smx_energy_frames_device_f32": (cint, [cint, f64, i64, i64, vp, i64, i64, i64, i64, vp, vp]),
+    "smx_yin_f32": (cint, [vp, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
+    "smx_yin_f64": (cint, [vp, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
+    "smx_yin_resident_f32": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp, vp]),
+    "smx_yin_difference_f32": (cint, [vp, i64, i64, i64, f64, f64, i64, i64, vp]),
+    "smx_yin_difference_f64": (cint, [vp, i64, i64, i64, f64, f64, i64, i64, vp]),
+    "smx_yin_difference_resident_f32": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, vp, vp]),
+    "smx_yin_frames_f32": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
+    "smx_yin_frames_f64": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
+    "smx_yin_frames_resident_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp, vp]),
     "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),

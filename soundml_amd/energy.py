@@ -178,6 +178,7 @@ class EnergyStage:
         self.op, self.frame_length, self.hop, self.threshold = int(op), int(frame_length), int(hop), float(threshold)
         # energy.ml:514-525: frame_length, hop, then the threshold, worded by the ABI
         check(lib.smx_energy_frames_f32(self.op, self.threshold, self.frame_length, self.hop, None, 0, 0, 0, None))
+        self.name = _NAMES[self.op] + "_stage"
         self.border = self.frame_length // 2
         self.latency = self.border                       # energy.ml:432
         self.rate = (1, self.hop)                        # energy.ml:445
@@ -201,7 +202,7 @@ class EnergyStage:
         if count == 0:
             self._pending = samples if fresh else _copy(samples)
             return None
-        out = segment_frames(self.op, samples, count, fl, hop, self.threshold)
+        out = self._segment(samples, count)
         next_start = count * hop
         if next_start >= total:
             self._skip += next_start - total
@@ -209,6 +210,10 @@ class EnergyStage:
         else:
             self._pending = _copy(samples[..., next_start:])
         return out
+
+    def _segment(self, samples, count):
+        """frames [0, count) of a segment of the padded stream"""
+        return segment_frames(self.op, samples, count, self.frame_length, self.hop, self.threshold)
 
     def step(self, chunk):
         if self._drained:
@@ -221,8 +226,8 @@ class EnergyStage:
         m = int(shape[-1])
         if m == 0:
             return None
-        b = Batch(chunk, _NAMES[self.op] + "_stage")
-        _refuse_device_float64(_NAMES[self.op] + "_stage", b)
+        b = Batch(chunk, self.name)
+        _refuse_device_float64(self.name, b)
         chunk = b.data if b.device or not b.torch else b.wrap(b.data)   # float32 / float64, contiguous, the caller's container
         self._tail = _copy(chunk[..., m - 1:])
         if not self._started:
