@@ -603,6 +603,81 @@ int smx_yin_frames_resident_f32(const float *d_x, int64_t lead, int64_t n, int64
                                 double fmin, double fmax, int64_t frame_length, int64_t hop, double trough_threshold,
                                 float *d_f0, float *d_aperiodicity, void *stream);
 
+/* ---- Rhythm: tempogram, tempo and beat tracking over an onset envelope (not in the reference) -------------------------------
+ * env [lead; frames] is an onset envelope (onset_strength's output).  Everything is float64 inside with one rounding into the
+ * dtype of the input; every sum has ONE order, a function of the clip's own values, so a leading slice of a
+ * batch equals the batch's slice and both tempogram kernels (SMX_DISABLE_FAST) give the same bits.  No chain is fused: a
+ * product and the sum it joins round one after the other.
+ *
+ * tempogram (Grosche, Mueller & Kurth 2010) -> [lead; win_length; frames], W = win_length, b = W / 2:
+ *   pad = b virtual zeros, env, W - b virtual zeros (zeros as for rms, not a ramp);  y_j = w_j pad[t + j], j < W, w the
+ *   periodic window of smx_window_make_param in float64, the product rounded once;
+ *   a(tau) = sum_{j < W - tau} y_j y_{j + tau}, tau = 0 .. W - 1: one ascending chain over j from 0.0;
+ *   norm != 0: a(tau) / a(0) unless a(0) < DBL_MIN, where a(tau) stays as it is; a frame that reads a NaN has a(0) = NaN and
+ *   is NaN at every lag then (without norm only the lags whose chain meets the NaN are).
+ * tempo -> [lead]:
+ *   m(tau) = (sum_t n(tau, t)) / frames over the float64 normalised tempogram n (hann window) before its rounding, one
+ *   ascending chain over t from 0.0, then the division;  bpm(tau) = 60 sample_rate / (hop tau);
+ *   prior(tau) = -0.5 ((log2 bpm(tau) - log2 start_bpm) / std_bpm)^2, -inf for tau = 0 and where bpm(tau) > max_tempo;
+ *   score(tau) = log1p(1e6 m(tau)) + prior(tau) over the lags whose prior is finite; the lag is the smallest tau that attains
+ *   the greatest score that is not NaN.  The result is bpm(lag), or the lag itself with want_lag; NaN when m(1) is NaN (a
+ *   non-finite or empty envelope) or no score is a number.  The float32 tempogram is never written.
+ * beat_track (Ellis 2007) -> tempo [lead], beats [lead; frames] as 1.0 / 0.0:
+ *   period = the lag of tempo (std_bpm 1, max_tempo 320) when has_bpm = 0, the integer itself, and the tempo reported is
+ *   bpm(lag); otherwise round_half_even(60 sample_rate / hop / bpm) and the tempo reported is bpm.  A clip has NO beats
+ *   (the mask is zeros, the tempo is still reported) when frames < 2, the lag is none, sd below is zero or not finite, or
+ *   some ls is not finite.
+ *   sd = sqrt((sum_i (env_i - mean)^2) / (frames - 1)), mean = (sum_i env_i) / frames: two ascending chains from 0.0;
+ *   ne = env / sd;  ls_i = sum_n ne_n g(i - n) over max(0, i - period) <= n <= min(frames - 1, i + period), one ascending
+ *   chain over n from 0.0;  g(k) = exp(-0.5 (32 k / period)^2);
+ *   window_k = -2 period + k, k = 0 .. 2 period - round_half_even(period / 2);  tx_k = -tightness log(-window_k / period)^2;
+ *   for i ascending: cand_k = tx_k + cum[i + window_k], tx_k alone where i + window_k < 0; k* the smallest k that attains
+ *   the maximum; cum_i = ls_i + cand_k*; back_i = -1 while no frame j <= i has had ls_j >= 0.01 max(ls), else i + window_k*;
+ *   local maxima: i >= 1 with cum_i > cum_{i-1} and (i = frames - 1 or cum_i >= cum_{i+1}); med = their median by exact
+ *   selection, (lo + hi) / 2 of the two middle values for an even count; the last beat is the largest maximum i with
+ *   2 cum_i > med (none: no beats); the beats are i, back_i, back_back_i .. while the index is >= 0;
+ *   trimming, over the beats in ascending order with v_q = ls at beat q: sm_q = (0.5 v_{q-1} + v_q) + 0.5 v_{q+1}, an absent
+ *   neighbour's term left out; th = 0.5 sqrt((sum_q sm_q^2) / count), an ascending chain, with trim, else 0; the beats from the
+ *   first to the last one with sm_q > th stay.
+ *   g, tx and the prior are built on the host in float64 with libm, once per (period range, tightness) / per prior, and kept on
+ *   the device; smx_rhythm_beat_tables (g [2 period + 1], tx [2 period - round_half_even(period / 2) + 1]),
+ *   smx_rhythm_tempo_prior and smx_rhythm_tempo_frequencies ([win_length] each) return the same values.
+ * Checks, in this order, before the data is looked at (null data and zero extents check the parameters only):
+ *   tempogram: win_length in [1, 16384], the window's parameter.
+ *   tempo, tempo_prior: sample_rate >= 1, hop >= 1, win_length, start_bpm finite and positive, std_bpm finite and positive,
+ *   max_tempo positive, some lag 1 .. win_length - 1 with bpm(lag) <= max_tempo.
+ *   beat_track: sample_rate, hop; with has_bpm: bpm finite and positive, its period in [1, 4096]; otherwise tempo's checks;
+ *   tightness finite and positive; then frames <= 8192.
+ * The device-resident forms end in `_gpu_f32` (tests/test_gpu_placement_rhythm.py keeps their table and law): rows
+ * env_stride >= frames apart, enqueued on `stream`, nothing synchronises it and no flag is read back. */
+int smx_rhythm_tempogram_f32(const float *env, int64_t lead, int64_t frames, int64_t win_length, int window,
+                             double window_param, int norm, float *out);
+int smx_rhythm_tempogram_f64(const double *env, int64_t lead, int64_t frames, int64_t win_length, int window,
+                             double window_param, int norm, double *out);
+int smx_rhythm_tempogram_gpu_f32(const float *d_env, int64_t lead, int64_t frames, int64_t env_stride, int64_t win_length,
+                                 int window, double window_param, int norm, float *d_out, void *stream);
+int smx_rhythm_tempo_f32(const float *env, int64_t lead, int64_t frames, int64_t sample_rate, int64_t hop, int64_t win_length,
+                         double start_bpm, double std_bpm, double max_tempo, int want_lag, float *out);
+int smx_rhythm_tempo_f64(const double *env, int64_t lead, int64_t frames, int64_t sample_rate, int64_t hop, int64_t win_length,
+                         double start_bpm, double std_bpm, double max_tempo, int want_lag, double *out);
+int smx_rhythm_tempo_gpu_f32(const float *d_env, int64_t lead, int64_t frames, int64_t env_stride, int64_t sample_rate,
+                             int64_t hop, int64_t win_length, double start_bpm, double std_bpm, double max_tempo, int want_lag,
+                             float *d_out, void *stream);
+int smx_rhythm_beat_track_f32(const float *env, int64_t lead, int64_t frames, int64_t sample_rate, int64_t hop, int has_bpm,
+                              double bpm, int64_t win_length, double start_bpm, double tightness, int trim, float *tempo,
+                              float *beats);
+int smx_rhythm_beat_track_f64(const double *env, int64_t lead, int64_t frames, int64_t sample_rate, int64_t hop, int has_bpm,
+                              double bpm, int64_t win_length, double start_bpm, double tightness, int trim, double *tempo,
+                              double *beats);
+int smx_rhythm_beat_track_gpu_f32(const float *d_env, int64_t lead, int64_t frames, int64_t env_stride, int64_t sample_rate,
+                                  int64_t hop, int has_bpm, double bpm, int64_t win_length, double start_bpm, double tightness,
+                                  int trim, float *d_tempo, float *d_beats, void *stream);
+int smx_rhythm_tempo_frequencies(int64_t win_length, int64_t sample_rate, int64_t hop, double *out);
+int smx_rhythm_tempo_prior(int64_t win_length, int64_t sample_rate, int64_t hop, double start_bpm, double std_bpm,
+                           double max_tempo, double *out);
+int smx_rhythm_beat_period(int64_t sample_rate, int64_t hop, double bpm, int64_t *period);
+int smx_rhythm_beat_tables(int64_t period, double tightness, double *g, double *tx);
+
 /* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
  * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
  * independent planes):

@@ -153,6 +153,19 @@ SIGNATURES = {
     "smx_yin_frames_f32": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
     "smx_yin_frames_f64": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
     "smx_yin_frames_resident_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp, vp]),
+    "smx_rhythm_tempogram_f32": (cint, [vp, i64, i64, i64, cint, f64, cint, vp]),
+    "smx_rhythm_tempogram_f64": (cint, [vp, i64, i64, i64, cint, f64, cint, vp]),
+    "smx_rhythm_tempogram_gpu_f32": (cint, [vp, i64, i64, i64, i64, cint, f64, cint, vp, vp]),
+    "smx_rhythm_tempo_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, cint, vp]),
+    "smx_rhythm_tempo_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, cint, vp]),
+    "smx_rhythm_tempo_gpu_f32": (cint, [vp, i64, i64, i64, i64, i64, i64, f64, f64, f64, cint, vp, vp]),
+    "smx_rhythm_beat_track_f32": (cint, [vp, i64, i64, i64, i64, cint, f64, i64, f64, f64, cint, vp, vp]),
+    "smx_rhythm_beat_track_f64": (cint, [vp, i64, i64, i64, i64, cint, f64, i64, f64, f64, cint, vp, vp]),
+    "smx_rhythm_beat_track_gpu_f32": (cint, [vp, i64, i64, i64, i64, i64, cint, f64, i64, f64, f64, cint, vp, vp, vp]),
+    "smx_rhythm_tempo_frequencies": (cint, [i64, i64, i64, vp]),
+    "smx_rhythm_tempo_prior": (cint, [i64, i64, i64, f64, f64, f64, vp]),
+    "smx_rhythm_beat_period": (cint, [i64, i64, f64, pi64]),
+    "smx_rhythm_beat_tables": (cint, [i64, f64, vp, vp]),
     "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
