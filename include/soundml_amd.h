@@ -678,6 +678,68 @@ int smx_rhythm_tempo_prior(int64_t win_length, int64_t sample_rate, int64_t hop,
 int smx_rhythm_beat_period(int64_t sample_rate, int64_t hop, double bpm, int64_t *period);
 int smx_rhythm_beat_tables(int64_t period, double tightness, double *g, double *tx);
 
+/* ---- Sequence: pairwise cost matrix and dynamic time warping of two feature sequences (not in the reference) ----------------
+ * X [pairs; d; n] and Y [pairs; d; m] are feature-major with frames last (chroma, MFCC, mel), pair by pair.  Everything is
+ * float64 inside with one rounding into the dtype of the input.
+ *
+ * 1. Cost.  C[i, j] is a function of column i of X and column j of Y only.  Every metric is ONE ascending chain over the
+ *    feature index k from 0.0, each operation rounded as written, nothing fused (x_k - y_k of float32 values is not always
+ *    exact in float64, so no fma):
+ *      SMX_METRIC_SQEUCLIDEAN  sum_k (x_k - y_k)^2
+ *      SMX_METRIC_EUCLIDEAN    its IEEE sqrt
+ *      SMX_METRIC_CITYBLOCK    sum_k |x_k - y_k|
+ *      SMX_METRIC_COSINE       1 - dot / (sqrt(xx) sqrt(yy)), dot = sum_k x_k y_k, xx = sum_k x_k x_k, yy = sum_k y_k y_k: three
+ *                              such chains; NaN where a norm is zero, as 0 / 0 is.
+ * 2. Recursion.  The steps are, in this order, s = 0 from (i - 1, j - 1), s = 1 from (i, j - 1), s = 2 from (i - 1, j):
+ *      cand_s = (D[prev_s] + weights_mul[s] C[i, j]) + weights_add[s];
+ *    a step whose predecessor lies outside the matrix is absent.  D[i, j] is the first present candidate; each later present
+ *    candidate replaces it only if cand < best, a strict comparison and never fmin: a tie keeps the earlier step, a NaN never
+ *    replaces anything, a NaN that came first stays.  The chosen s is the cell's step code.  D[0, 0] = C[0, 0], unweighted.
+ *    With subseq, D[0, j] = C[0, j] for every j: row 0 has no predecessors.
+ * 3. End and path.  The end cell is (n - 1, m - 1); with subseq (n - 1, j*), j* chosen by the same rule over row n - 1 in
+ *    float64: start from j = 0, replace only if strictly smaller, so the smallest index wins ties.  The path follows the step
+ *    codes back from the end until (0, 0), or until i = 0 with subseq, and is written in ascending order into path
+ *    [pairs; 2; n + m - 1] in the dtype of the input: row 0 the indices into X, row 1 those into Y, the unused tail of both
+ *    rows -1.0.  dtw_distance [pairs] is the float64 value at the end cell, rounded once; it writes neither D nor step codes.
+ * Nothing in 2 and 3 depends on the order in which cells are visited (+ and < on the same operands give the same bits): the
+ * tile kernel (smx_sequence_tile gives its tile shape), the general kernel (SMX_DISABLE_FAST=1, and every float64 call), a
+ * leading slice of a batch and the batch's slice agree bit for bit.
+ * Checks, in this order, before the data is looked at (null data and zero pairs check the parameters only): the metric;
+ * d >= 1; n >= 1 and m >= 1; dtw and dtw_distance: every weight finite; dtw: n m <= 2^29 (the step codes of one pair, a byte a
+ * cell, are the scratch of one launch group: 512 MB; dtw_distance has no such cap), and n, m <= 2^24 in float32 (the path's
+ * indices are exact).  Scratch is stream-ordered, at most 512 MB per launch group where one pair fits; larger batches go pair
+ * range by pair range.
+ * Out of scope: step sets other than the classic three; global band constraints (Sakoe-Chiba band, Itakura parallelogram); a
+ * streaming stage (the alignment is offline by definition: the end cell needs both sequences whole); recurrence and
+ * self-similarity matrices beyond what cost_matrix(X, X) gives.
+ * The device-resident forms end in `_hbm_f32` (tests/test_gpu_placement_sequence.py keeps their table and law): rows of X
+ * x_stride >= n and rows of Y y_stride >= m elements apart, dense outputs, enqueued on `stream`, nothing synchronises it and no
+ * flag is read back. */
+#define SMX_METRIC_EUCLIDEAN 0
+#define SMX_METRIC_SQEUCLIDEAN 1
+#define SMX_METRIC_CITYBLOCK 2
+#define SMX_METRIC_COSINE 3
+int smx_sequence_tile(int64_t *rows, int64_t *cols);
+int smx_cost_matrix_f32(const float *x, const float *y, int64_t pairs, int64_t d, int64_t n, int64_t m, int metric, float *out);
+int smx_cost_matrix_f64(const double *x, const double *y, int64_t pairs, int64_t d, int64_t n, int64_t m, int metric,
+                        double *out);
+int smx_cost_matrix_hbm_f32(const float *d_x, const float *d_y, int64_t pairs, int64_t d, int64_t n, int64_t m, int64_t x_stride,
+                            int64_t y_stride, int metric, float *d_out, void *stream);
+int smx_dtw_f32(const float *x, const float *y, int64_t pairs, int64_t d, int64_t n, int64_t m, int metric,
+                const double *weights_add, const double *weights_mul, int subseq, float *D, float *path);
+int smx_dtw_f64(const double *x, const double *y, int64_t pairs, int64_t d, int64_t n, int64_t m, int metric,
+                const double *weights_add, const double *weights_mul, int subseq, double *D, double *path);
+int smx_dtw_hbm_f32(const float *d_x, const float *d_y, int64_t pairs, int64_t d, int64_t n, int64_t m, int64_t x_stride,
+                    int64_t y_stride, int metric, const double *weights_add, const double *weights_mul, int subseq, float *d_D,
+                    float *d_path, void *stream);
+int smx_dtw_distance_f32(const float *x, const float *y, int64_t pairs, int64_t d, int64_t n, int64_t m, int metric,
+                         const double *weights_add, const double *weights_mul, int subseq, float *out);
+int smx_dtw_distance_f64(const double *x, const double *y, int64_t pairs, int64_t d, int64_t n, int64_t m, int metric,
+                         const double *weights_add, const double *weights_mul, int subseq, double *out);
+int smx_dtw_distance_hbm_f32(const float *d_x, const float *d_y, int64_t pairs, int64_t d, int64_t n, int64_t m, int64_t x_stride,
+                             int64_t y_stride, int metric, const double *weights_add, const double *weights_mul, int subseq,
+                             float *d_out, void *stream);
+
 /* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
  * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
  * independent planes):

@@ -44,6 +44,7 @@ WINDOW_PARAMETRIC = ("kaiser", "gaussian", "tukey")
 MEL_SCALE = {"slaney": 0, "htk": 1}
 MEL_NORM = {"slaney": 0, "none": 1}
 INTERIOR = {"float32": 0, "float64": 1}
+METRIC = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "cosine": 3}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -166,6 +167,16 @@ SIGNATURES = {
     "smx_rhythm_tempo_prior": (cint, [i64, i64, i64, f64, f64, f64, vp]),
     "smx_rhythm_beat_period": (cint, [i64, i64, f64, pi64]),
     "smx_rhythm_beat_tables": (cint, [i64, f64, vp, vp]),
+    "smx_sequence_tile": (cint, [pi64, pi64]),
+    "smx_cost_matrix_f32": (cint, [vp, vp, i64, i64, i64, i64, cint, vp]),
+    "smx_cost_matrix_f64": (cint, [vp, vp, i64, i64, i64, i64, cint, vp]),
+    "smx_cost_matrix_hbm_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, i64, cint, vp, vp]),
+    "smx_dtw_f32": (cint, [vp, vp, i64, i64, i64, i64, cint, pf64, pf64, cint, vp, vp]),
+    "smx_dtw_f64": (cint, [vp, vp, i64, i64, i64, i64, cint, pf64, pf64, cint, vp, vp]),
+    "smx_dtw_hbm_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, i64, cint, pf64, pf64, cint, vp, vp, vp]),
+    "smx_dtw_distance_f32": (cint, [vp, vp, i64, i64, i64, i64, cint, pf64, pf64, cint, vp]),
+    "smx_dtw_distance_f64": (cint, [vp, vp, i64, i64, i64, i64, cint, pf64, pf64, cint, vp]),
+    "smx_dtw_distance_hbm_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, i64, cint, pf64, pf64, cint, vp, vp]),
     "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
