@@ -740,6 +740,79 @@ int smx_dtw_distance_hbm_f32(const float *d_x, const float *d_y, int64_t pairs, 
                              int64_t y_stride, int metric, const double *weights_add, const double *weights_mul, int subseq,
                              float *d_out, void *stream);
 
+/* ---- Decompose: non-negative matrix factorisation of a magnitude spectrogram (not in the reference) -------------------------
+ * V [clips; F; T] >= 0 is feature-major with frames last; W [clips; F; K] holds K spectral templates per clip and H [clips; K; T]
+ * their activations, V ~ W H.  Multiplicative updates (Lee & Seung 2001); beta is SMX_NMF_FROBENIUS or SMX_NMF_KULLBACK_LEIBLER.
+ * Results have the dtype of V; the interior is float32 for float32 and float64 for float64.
+ *
+ * eps = 2^-23 (1.1920929e-07); floor(x) is `x < eps ? eps : x`, so a NaN stays a NaN.  One round is two updates in this order,
+ * the W update seeing the new H:
+ *   H update, Frobenius   H <- (H o (W^T V)) / floor((W^T W) H)
+ *   H update, KL          R = V / floor(W H);  H <- (H o (W^T R)) / floor(s_k),  s_k = sum_f W[f, k] 1 for every entry of row k
+ *   W update, Frobenius   W <- (W o (V H^T)) / floor(W (H H^T))
+ *   W update, KL          R = V / floor(W H);  W <- (W o (R H^T)) / floor(s_k),  s_k = sum_t H[k, t] 1 for every entry of column k
+ * The product with the old factor and the IEEE division round one after the other.  Every inner product (the entries of W^T V,
+ * W^T W, (W^T W) H, W H, W^T R, s_k and their transposes) is ONE chain acc = fma(a, b, acc) from 0.0 whose order is a function of
+ * (F, T, K) only, never of the batch, the grid, the clip or the kernel:
+ *   over f or t   32-block after 32-block in ascending order; inside a block the offsets run
+ *                 0 4 1 5 2 6 3 7 | 8 12 9 13 10 14 11 15 | 16 20 ... | 24 28 ... 27 31, i.e. position i = 2 r + h is offset
+ *                 (r & 3) + 8 (r >> 2) + 4 h (the order in which a 32 x 32 accumulator tile of v_mfma_f32_32x32x2_f32 hands its
+ *                 rows on as the next product's operand); the last block is padded to 32 with terms fma(0, 0, acc)
+ *   over k        ascending, padded to an even count with one term fma(0, 0, acc)
+ * (a pad term changes nothing but the sign of a zero sum).  The tile kernels (float32, K <= 64: smx_nmf_tile_cap) and the general
+ * kernels (any K <= 1024, float64, SMX_DISABLE_FAST=1), a leading slice of a batch and the batch's slice agree bit for bit, and
+ * n_iter = a continued by n_iter = b from its factors equals n_iter = a + b.  n_iter = 0 returns the initial factors.
+ * A NaN in V[f, t] makes column t of H and every entry of W NaN in the first round and every entry of H of that clip in the
+ * second; no other clip is touched.  Negative entries are not checked.
+ * nmf_activations runs the H update alone with W fixed; the device form takes w_stride = 0 for ONE dictionary [F; K] shared by
+ * every clip.  nmf_reconstruct is W H by the chain over k above, a component outside `components` (n_components indices on the
+ * host; null: all of them) entering as fma(0, 0, acc); with as_mask the result is that sum over floor(the sum of all components),
+ * the soft mask of the chosen components.  nmf_divergence [clips] is the objective per clip in float64 from the
+ * stored factors, X = W H an ascending chain over k of products and sums rounded one after the other:
+ *   Frobenius   sqrt(sum (V - X)^2 / sum V^2)
+ *   KL          ((sum over V > 0 of V log(V / X)) - sum V + sum X) / sum V
+ * every sum an ascending chain over t per row, then an ascending chain over the rows, rounded once into the dtype of V.
+ * Checks, in this order, before the data is looked at (null data and zero clips check the parameters only): K >= 1; K <= 1024;
+ * F, T >= 1 and <= 2^24; beta; n_iter >= 0; clips >= 0; the pitches and strides below.  Scratch is stream-ordered, at most 512 MB
+ * per launch group where one clip fits; larger batches go clip range by clip range, each range running all its rounds.
+ * Out of scope: the Itakura-Saito divergence; sparsity penalties; a dictionary learned across clips (a reduction across clips);
+ * streaming; convolutive NMF.
+ * The device-resident forms end in `_vram_f32` (tests/test_gpu_placement_decompose.py keeps their table and law): clips of V
+ * v_stride and its rows v_pitch >= T elements apart (S[..., :, a:b] of a spectrogram is an input as it stands), the factors'
+ * clips w0_stride, h0_stride, w_stride, h_stride elements apart, dense inside a clip; nmf_reconstruct's output out_stride /
+ * out_pitch apart.  Results must not overlap inputs.  Enqueued on `stream`, nothing synchronises it and no flag is read back. */
+#define SMX_NMF_FROBENIUS 0
+#define SMX_NMF_KULLBACK_LEIBLER 1
+int smx_nmf_tile_cap(int64_t *tile_k, int64_t *max_k);
+int smx_nmf_f32(const float *V, const float *W0, const float *H0, int64_t clips, int64_t F, int64_t T, int64_t K, int64_t n_iter,
+                int beta, float *W, float *H);
+int smx_nmf_f64(const double *V, const double *W0, const double *H0, int64_t clips, int64_t F, int64_t T, int64_t K,
+                int64_t n_iter, int beta, double *W, double *H);
+int smx_nmf_vram_f32(const float *d_V, int64_t v_stride, int64_t v_pitch, const float *d_W0, int64_t w0_stride, const float *d_H0,
+                     int64_t h0_stride, int64_t clips, int64_t F, int64_t T, int64_t K, int64_t n_iter, int beta, float *d_W,
+                     int64_t w_stride, float *d_H, int64_t h_stride, void *stream);
+int smx_nmf_activations_f32(const float *V, const float *W, const float *H0, int64_t clips, int64_t F, int64_t T, int64_t K,
+                            int64_t n_iter, int beta, float *H);
+int smx_nmf_activations_f64(const double *V, const double *W, const double *H0, int64_t clips, int64_t F, int64_t T, int64_t K,
+                            int64_t n_iter, int beta, double *H);
+int smx_nmf_activations_vram_f32(const float *d_V, int64_t v_stride, int64_t v_pitch, const float *d_W, int64_t w_stride,
+                                 const float *d_H0, int64_t h0_stride, int64_t clips, int64_t F, int64_t T, int64_t K,
+                                 int64_t n_iter, int beta, float *d_H, int64_t h_stride, void *stream);
+int smx_nmf_reconstruct_f32(const float *W, const float *H, int64_t clips, int64_t F, int64_t T, int64_t K,
+                            const int64_t *components, int64_t n_components, int as_mask, float *out);
+int smx_nmf_reconstruct_f64(const double *W, const double *H, int64_t clips, int64_t F, int64_t T, int64_t K,
+                            const int64_t *components, int64_t n_components, int as_mask, double *out);
+int smx_nmf_reconstruct_vram_f32(const float *d_W, int64_t w_stride, const float *d_H, int64_t h_stride, int64_t clips, int64_t F,
+                                 int64_t T, int64_t K, const int64_t *components, int64_t n_components, int as_mask,
+                                 float *d_out, int64_t out_stride, int64_t out_pitch, void *stream);
+int smx_nmf_divergence_f32(const float *V, const float *W, const float *H, int64_t clips, int64_t F, int64_t T, int64_t K,
+                           int beta, float *out);
+int smx_nmf_divergence_f64(const double *V, const double *W, const double *H, int64_t clips, int64_t F, int64_t T, int64_t K,
+                           int beta, double *out);
+int smx_nmf_divergence_vram_f32(const float *d_V, int64_t v_stride, int64_t v_pitch, const float *d_W, int64_t w_stride,
+                                const float *d_H, int64_t h_stride, int64_t clips, int64_t F, int64_t T, int64_t K, int beta,
+                                float *d_out, void *stream);
+
 /* ---- Harmonic/percussive separation (hpss.ml) ------------------------------------------------------------
  * Median-filter separation of a magnitude spectrogram s [lead; bins; frames] (frames fastest; leading axes are
  * independent planes):

@@ -45,6 +45,7 @@ MEL_SCALE = {"slaney": 0, "htk": 1}
 MEL_NORM = {"slaney": 0, "none": 1}
 INTERIOR = {"float32": 0, "float64": 1}
 METRIC = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "cosine": 3}
+BETA = {"frobenius": 0, "kullback-leibler": 1}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -177,6 +178,19 @@ SIGNATURES = {
     "smx_dtw_distance_f32": (cint, [vp, vp, i64, i64, i64, i64, cint, pf64, pf64, cint, vp]),
     "smx_dtw_distance_f64": (cint, [vp, vp, i64, i64, i64, i64, cint, pf64, pf64, cint, vp]),
     "smx_dtw_distance_hbm_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, i64, cint, pf64, pf64, cint, vp, vp]),
+    "smx_nmf_tile_cap": (cint, [vp, vp]),
+    "smx_nmf_f32": (cint, [vp, vp, vp, i64, i64, i64, i64, i64, cint, vp, vp]),
+    "smx_nmf_f64": (cint, [vp, vp, vp, i64, i64, i64, i64, i64, cint, vp, vp]),
+    "smx_nmf_vram_f32": (cint, [vp, i64, i64, vp, i64, vp, i64, i64, i64, i64, i64, i64, cint, vp, i64, vp, i64, vp]),
+    "smx_nmf_activations_f32": (cint, [vp, vp, vp, i64, i64, i64, i64, i64, cint, vp]),
+    "smx_nmf_activations_f64": (cint, [vp, vp, vp, i64, i64, i64, i64, i64, cint, vp]),
+    "smx_nmf_activations_vram_f32": (cint, [vp, i64, i64, vp, i64, vp, i64, i64, i64, i64, i64, i64, cint, vp, i64, vp]),
+    "smx_nmf_reconstruct_f32": (cint, [vp, vp, i64, i64, i64, i64, vp, i64, cint, vp]),
+    "smx_nmf_reconstruct_f64": (cint, [vp, vp, i64, i64, i64, i64, vp, i64, cint, vp]),
+    "smx_nmf_reconstruct_vram_f32": (cint, [vp, i64, vp, i64, i64, i64, i64, i64, vp, i64, cint, vp, i64, i64, vp]),
+    "smx_nmf_divergence_f32": (cint, [vp, vp, vp, i64, i64, i64, i64, cint, vp]),
+    "smx_nmf_divergence_f64": (cint, [vp, vp, vp, i64, i64, i64, i64, cint, vp]),
+    "smx_nmf_divergence_vram_f32": (cint, [vp, i64, i64, vp, i64, vp, i64, i64, i64, i64, i64, cint, vp, vp]),
     "smx_hpss_masks_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f64": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp]),
     "smx_hpss_masks_f32_dev": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, f64, vp, vp, vp]),
