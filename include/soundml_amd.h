@@ -603,6 +603,99 @@ int smx_yin_frames_resident_f32(const float *d_x, int64_t lead, int64_t n, int64
                                 double fmin, double fmax, int64_t frame_length, int64_t hop, double trough_threshold,
                                 float *d_f0, float *d_aperiodicity, void *stream);
 
+/* ---- Pitch, continued: pYIN (Mauch & Dixon 2014; not in the reference) -------------------------------------------------------
+ * Probabilistic YIN with Viterbi decoding.  Audio x [lead; n] -> f0, voiced_flag (1.0 / 0.0) and voiced_prob, each
+ * [lead; frames]; or the observation [lead; 2 n_bins; frames]; or, from an observation, the decoded states [lead; frames]
+ * (exact integers; state s < n_bins is voiced bin s, n_bins + b is unvoiced bin b).  The grid is yin's, everything is float64
+ * inside with one rounding into the dtype of the input, and there is ONE order of operations, restated in
+ * tests/pyin_restatement.py.  The decoder is offline by definition: there is no streaming stage.
+ *
+ * Host tables (float64, libm; smx_pyin_tables returns them), n = n_thresholds, (a, b) = beta parameters, l = boltzmann_parameter:
+ *   thr[k] = k / n, k = 0 .. n;   beta[k] = I(thr[k + 1]; a, b) - I(thr[k]; a, b), I the regularised incomplete beta function
+ *   E[q] = exp(-l q);   Z[N] = (1 - exp(-l)) / (1 - exp(-l N)), N >= 1;  the trough prior is the ONE product Z[N] * E[q]
+ *   bps = ceil(1 / resolution);   n_bins = floor(12 bps log2(fmax / fmin)) + 1;   freq[b] = fmin 2^(b / (12 bps))
+ *   edge[b] = fmin 2^((b - 0.5) / (12 bps)), b = 1 .. n_bins - 1: the bin of a frequency f is the number of edges <= f
+ *   (comparisons only; it lies in [0, n_bins - 1])
+ *   m = round-half-even(max_transition_rate 12 hop / sample_rate), h = (m bps) / 2 (integer division)
+ *   tri[k] = 1 - |k - h| / (h + 1), k = 0 .. 2 h;   rs[i] = 1 / (the sum of tri[j - i + h] over the j of [i - h, i + h] that lie
+ *   in [0, n_bins), ascending)
+ *
+ * Observation, per frame, from yin's float64 d'(tau) (its chains, its bits):
+ *   1. the troughs: tau in [pmin, pmax] with d'(tau) <= d'(tau - 1) and (tau = pmax or d'(tau) < d'(tau + 1)): yin's rule without
+ *      the threshold; tau_1 < .. < tau_R with heights g_r
+ *   2. for k = 1 .. n: below(r, k) = g_r < thr[k], N_k their count, q(r, k) the number of r' < r with below(r', k); p_r adds, from
+ *      0.0 in ascending k, (Z[N_k] * E[q(r, k)]) * beta[k - 1] where below(r, k): each product rounded, then the sum
+ *   3. r* the first trough of least height, K0 the number of k in 1 .. n with thr[k] <= g_r*:
+ *      p_r* += no_trough_prob * (beta[0] + .. + beta[K0 - 1], ascending) where K0 < n; where no threshold lies above the least
+ *      trough (d' = 1 throughout: silence) nothing is added, the frame has voiced_prob = 0
+ *   4. every r with p_r > 0: period tau_r + shift_r (yin's parabola rule), f = sample_rate / period, its bin by edge; obs[b] adds
+ *      the p_r that land in b, from 0.0 in ascending r
+ *   5. voiced_prob = min(1, obs[0] + .. + obs[n_bins - 1], ascending)       6. obs[n_bins + b] = (1 - voiced_prob) / n_bins
+ *   7. a frame that yin would give NaN (e(0) or c(pmax) not finite) has a zero voiced part and voiced_prob = 0 for the decoder;
+ *      its voiced_prob and its column of pyin_observation are NaN
+ *
+ * Decode, per clip, in the probability domain: only *, < and an exact scaling by a power of two occur, no log is taken.
+ *   1. B = obs where obs > FLOOR, else FLOOR = 2^-200 (a NaN too): a path stays alive when a frame with voiced_prob = 1 jumps
+ *      further than the band
+ *   2. delta_0 = p_init * B_0, p_init = 1 / n_bins on the unvoiced states and 0 on the voiced
+ *   3. per frame t >= 1: u[i] = (delta[i] * 2^-e) * rs[i], e the binary exponent (frexp) of the greatest delta; per voicing v,
+ *      M_v(j) the greatest u_v[i] * tri[j - i + h] over the band's i in ascending order, a candidate replacing the best only if
+ *      strictly greater (the smallest i wins ties); a = M_v(j) * (1 - switch_prob), b = M_{1-v}(j) * switch_prob, b taken only if
+ *      b > a; delta_t(v, j) = taken * B_t(v, j), the back pointer the taken (v', i)
+ *   4. the end: the smallest state of the greatest delta_{T-1}; the walk back follows the pointers
+ *   5. f0 = freq[state mod n_bins] on voiced frames, `fill` on unvoiced ones (the bin's frequency with keep_bin != 0);
+ *      voiced_flag = 1 where state < n_bins
+ * One workgroup decodes a clip with delta, u and two frames' voiced observations in LDS: 3 n_bins + 2 min(h, n_bins - 1) may be at
+ * most 9212, past it the call is an argument error (there is no second decoder).
+ *
+ * Checks, in this order: yin's own (sample_rate, frame_length, hop, the band, pmax > pmin); n_thresholds >= 1; beta_a, beta_b
+ * finite and positive; boltzmann_parameter finite and positive; 0 < resolution < 1; max_transition_rate finite and >= 0;
+ * switch_prob and no_trough_prob in [0, 1]; 2 n_bins <= 65535; the band below 2^31 bins; (pyin) the decoder's cap.
+ * smx_pyin_decode: an even, positive state axis, half_width >= 0, switch_prob, 2 n_bins <= 65535, the cap.  Zero-size axes
+ * write nothing; a call with null data and zero extents checks the parameters only.
+ *
+ * The device-resident forms end in `_accel_f32` (tests/test_gpu_placement_pyin.py keeps their table and law): rows x_stride >= n
+ * apart (clips clip_stride >= states * frames apart), enqueued on `stream`; nothing synchronises it and no flag is read back. */
+int smx_pyin_f32(const float *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax, int64_t frame_length,
+                 int64_t hop, int64_t n_thresholds, double beta_a, double beta_b, double boltzmann_parameter, double resolution,
+                 double max_transition_rate, double switch_prob, double no_trough_prob, int64_t keep_bin, double fill, float *f0,
+                 float *voiced_flag, float *voiced_prob);
+int smx_pyin_f64(const double *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax, int64_t frame_length,
+                 int64_t hop, int64_t n_thresholds, double beta_a, double beta_b, double boltzmann_parameter, double resolution,
+                 double max_transition_rate, double switch_prob, double no_trough_prob, int64_t keep_bin, double fill, double *f0,
+                 double *voiced_flag, double *voiced_prob);
+int smx_pyin_accel_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t sample_rate, double fmin, double fmax,
+                       int64_t frame_length, int64_t hop, int64_t n_thresholds, double beta_a, double beta_b,
+                       double boltzmann_parameter, double resolution, double max_transition_rate, double switch_prob,
+                       double no_trough_prob, int64_t keep_bin, double fill, float *d_f0, float *d_voiced_flag,
+                       float *d_voiced_prob, void *stream);
+int smx_pyin_observation_f32(const float *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax,
+                             int64_t frame_length, int64_t hop, int64_t n_thresholds, double beta_a, double beta_b,
+                             double boltzmann_parameter, double resolution, double max_transition_rate, double switch_prob,
+                             double no_trough_prob, float *out);
+int smx_pyin_observation_f64(const double *x, int64_t lead, int64_t n, int64_t sample_rate, double fmin, double fmax,
+                             int64_t frame_length, int64_t hop, int64_t n_thresholds, double beta_a, double beta_b,
+                             double boltzmann_parameter, double resolution, double max_transition_rate, double switch_prob,
+                             double no_trough_prob, double *out);
+int smx_pyin_observation_accel_f32(const float *d_x, int64_t lead, int64_t n, int64_t x_stride, int64_t sample_rate, double fmin,
+                                   double fmax, int64_t frame_length, int64_t hop, int64_t n_thresholds, double beta_a,
+                                   double beta_b, double boltzmann_parameter, double resolution, double max_transition_rate,
+                                   double switch_prob, double no_trough_prob, float *d_out, void *stream);
+int smx_pyin_decode_f32(const float *obs, int64_t lead, int64_t states, int64_t frames, int64_t half_width, double switch_prob,
+                        float *out);
+int smx_pyin_decode_f64(const double *obs, int64_t lead, int64_t states, int64_t frames, int64_t half_width, double switch_prob,
+                        double *out);
+int smx_pyin_decode_accel_f32(const float *d_obs, int64_t lead, int64_t states, int64_t frames, int64_t clip_stride,
+                              int64_t half_width, double switch_prob, float *d_out, void *stream);
+/* n_bins; h; and the host tables thr [n + 1], beta [n], E [maxr], Z [maxr + 1] (Z[0] = 0), freq [n_bins], edge [n_bins - 1]
+ * (b = 1 ..), tri [2 h + 1], rs [n_bins], maxr = (pmax - pmin) / 2 + 1 the most troughs of a frame; each may be NULL */
+int smx_pyin_bins(double fmin, double fmax, double resolution, int64_t *n_bins);
+int smx_pyin_half_width(int64_t sample_rate, int64_t hop, double resolution, double max_transition_rate, int64_t *half_width);
+int smx_pyin_tables(int64_t sample_rate, double fmin, double fmax, int64_t frame_length, int64_t hop, int64_t n_thresholds,
+                    double beta_a, double beta_b, double boltzmann_parameter, double resolution, double max_transition_rate,
+                    double switch_prob, double no_trough_prob, double *thr, double *beta, double *E, double *Z, double *freq,
+                    double *edge, double *tri, double *rs);
+
 /* ---- Rhythm: tempogram, tempo and beat tracking over an onset envelope (not in the reference) -------------------------------
  * env [lead; frames] is an onset envelope (onset_strength's output).  Everything is float64 inside with one rounding into the
  * dtype of the input; every sum has ONE order, a function of the clip's own values, so a leading slice of a

@@ -4,7 +4,7 @@ module names:
 
     from soundml_amd import Stft, Mel, Chroma, Cqt, Hpss, Window, Fir, Resample, resample, mel_spectrogram, mfcc, chroma_stft, chroma_cqt, spectral_centroid
     from soundml_amd import rms, rms_of_spectrogram, rms_stage, zero_crossing_rate, zero_crossing_rate_stage
-    from soundml_amd import Pitch, yin, yin_difference, yin_stage
+    from soundml_amd import Pitch, yin, yin_difference, yin_stage, pyin, pyin_observation, pyin_decode
     from soundml_amd import Rhythm, tempogram, tempo, beat_track
     from soundml_amd import Sequence, cost_matrix, dtw, dtw_distance
     from soundml_amd import Decompose, nmf, nmf_activations, nmf_reconstruct, nmf_divergence
@@ -34,7 +34,7 @@ from .contrast import spectral_contrast, spectral_contrast_of_spectrogram, spect
 from .onset import onset_strength, onset_strength_stage
 from .energy import rms, rms_of_spectrogram, rms_stage, zero_crossing_rate, zero_crossing_rate_stage
 from . import pitch as Pitch
-from .pitch import yin, yin_difference, yin_stage
+from .pitch import yin, yin_difference, yin_stage, pyin, pyin_observation, pyin_decode
 from . import rhythm as Rhythm
 from .rhythm import tempogram, tempo, beat_track
 from . import sequence as Sequence
@@ -89,5 +89,5 @@ def get_devices():
 
 
 __all__ = ["Stft", "Mel", "Chroma", "Cqt", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "chroma_cqt", "power_to_db", "amplitude_to_db", "spectral_centroid",
-           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_contrast_of_spectrogram", "spectral_contrast_stage", "onset_strength", "onset_strength_stage", "rms", "rms_of_spectrogram", "rms_stage", "zero_crossing_rate", "zero_crossing_rate_stage", "Pitch", "yin", "yin_difference", "yin_stage", "Rhythm", "tempogram", "tempo", "beat_track", "Sequence", "cost_matrix", "dtw", "dtw_distance", "Decompose", "nmf", "nmf_activations", "nmf_reconstruct", "nmf_divergence", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
+           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_contrast_of_spectrogram", "spectral_contrast_stage", "onset_strength", "onset_strength_stage", "rms", "rms_of_spectrogram", "rms_stage", "zero_crossing_rate", "zero_crossing_rate_stage", "Pitch", "yin", "yin_difference", "yin_stage", "pyin", "pyin_observation", "pyin_decode", "Rhythm", "tempogram", "tempo", "beat_track", "Sequence", "cost_matrix", "dtw", "dtw_distance", "Decompose", "nmf", "nmf_activations", "nmf_reconstruct", "nmf_divergence", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

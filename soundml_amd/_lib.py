@@ -155,6 +155,18 @@ SIGNATURES = {
     "smx_yin_frames_f32": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
     "smx_yin_frames_f64": (cint, [vp, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp]),
     "smx_yin_frames_resident_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, f64, i64, i64, f64, vp, vp, vp]),
+    "smx_pyin_f32": (cint, [vp, i64, i64] + [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [i64, f64, vp, vp, vp]),
+    "smx_pyin_f64": (cint, [vp, i64, i64] + [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [i64, f64, vp, vp, vp]),
+    "smx_pyin_accel_f32": (cint, [vp, i64, i64, i64] + [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [i64, f64, vp, vp, vp, vp]),
+    "smx_pyin_observation_f32": (cint, [vp, i64, i64] + [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [vp]),
+    "smx_pyin_observation_f64": (cint, [vp, i64, i64] + [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [vp]),
+    "smx_pyin_observation_accel_f32": (cint, [vp, i64, i64, i64] + [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [vp, vp]),
+    "smx_pyin_decode_f32": (cint, [vp, i64, i64, i64, i64, f64, vp]),
+    "smx_pyin_decode_f64": (cint, [vp, i64, i64, i64, i64, f64, vp]),
+    "smx_pyin_decode_accel_f32": (cint, [vp, i64, i64, i64, i64, i64, f64, vp, vp]),
+    "smx_pyin_bins": (cint, [f64, f64, f64, pi64]),
+    "smx_pyin_half_width": (cint, [i64, i64, f64, f64, pi64]),
+    "smx_pyin_tables": (cint, [i64, f64, f64, i64, i64, i64] + [f64] * 7 + [vp] * 8),
     "smx_rhythm_tempogram_f32": (cint, [vp, i64, i64, i64, cint, f64, cint, vp]),
     "smx_rhythm_tempogram_f64": (cint, [vp, i64, i64, i64, cint, f64, cint, vp]),
     "smx_rhythm_tempogram_gpu_f32": (cint, [vp, i64, i64, i64, i64, cint, f64, cint, vp, vp]),

@@ -365,7 +365,10 @@ __global__ void __launch_bounds__(64) beat_kernel(BeatArgs a) {
 
 // ---- the host side ---------------------------------------------------------------------------------------------------------------
 // tables on the device, built once per key and device and kept: the holder keeps its table alive through the enqueue; the
-// eviction's hipFree waits for the device, i.e. for every launch that reads it
+// eviction's hipFree waits for the device, i.e. for every launch that reads it (declared in smx_internal.hpp: pitch.hip keeps
+// pYIN's tables the same way)
+}  // namespace
+
 std::shared_ptr<void> cached_table(const std::string &key, const std::function<std::vector<unsigned char>()> &make) {
   static std::mutex mutex;
   static std::map<std::string, std::shared_ptr<void>> tables;
@@ -389,6 +392,8 @@ std::shared_ptr<void> cached_table(const std::string &key, const std::function<s
   tables[full] = owner;
   return owner;
 }
+
+namespace {
 
 template <typename V>
 std::vector<unsigned char> as_bytes(const std::vector<V> &v) {

@@ -646,6 +646,37 @@ int guarded(F &&body) {
   }
 }
 
+// ---- pYIN's decoder (pyin.hip; pitch.hip's pyin hands it the float64 observation) -------------------------------------------
+struct PyinDecodeJob {
+  const char *fn;
+  const void *d_obs;              // observation of `lead` clips, element (clip, state, frame) at clip clip_stride + state state_stride +
+  int obs_bytes;                  // frame frame_stride; float32 or float64
+  int64_t clip_stride, state_stride, frame_stride;
+  // or, d_obs null, pyin's sparse float64 observation, frames clip-major: the unvoiced states' value, the number of occupied voiced
+  // bins and their bins (ascending) and values, `list` entries per frame
+  const double *d_rest, *d_value;
+  const int *d_count, *d_bin;
+  int64_t list;
+  int64_t lead, frames, n_bins, half_width;
+  double switch_prob;
+  int elem_bytes;                 // of the results [lead; frames]
+  void *d_states;                 // the state of every frame, or null and
+  void *d_f0, *d_flag;            // freq[state mod n_bins] (`fill` on unvoiced frames unless keep_bin) and the 1.0 / 0.0 voiced flag
+  const double *d_freq;
+  bool keep_bin;
+  double fill;
+  hipStream_t stream;
+};
+void check_pyin_decode(const char *fn, int64_t n_bins, int64_t half_width, double switch_prob);   // words what it cannot take
+int64_t pyin_decode_scratch(int64_t frames, int64_t n_bins, int64_t half_width);                  // bytes per clip
+void launch_pyin_decode(const PyinDecodeJob &job);
+double pyin_triangle(int64_t k, int64_t h);                              // tri[k] = 1 - |k - h| / (h + 1)
+void pyin_band_scale(int64_t n_bins, int64_t h, double *rs);             // rs[i] = 1 / (the band's sum of tri over the targets in [0, n_bins))
+
+// A host-built table on the current device, built once per key and device and kept (rhythm.hip); the holder keeps it alive
+// through the enqueue
+std::shared_ptr<void> cached_table(const std::string &key, const std::function<std::vector<unsigned char>()> &make);
+
 inline void require_device() {
   int count = 0;
   hipError_t err = hipGetDeviceCount(&count);
