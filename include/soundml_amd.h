@@ -21,6 +21,13 @@
  *     hipStream_t (as void*); they enqueue work and return without
  *     synchronising.  The host-pointer entry points upload, run and download
  *     (this is what an nx-tensor caller uses).
+ *   - streams: every launch, memset, copy and scratch array of a call is ordered
+ *     on the caller's stream and on no other; only the entry points that say so
+ *     (the spectral-shape features and the flat spectral contrast of a
+ *     spectrogram, which read one flag back) wait for it, and they return with
+ *     it idle; configurations may be shared between streams.  The first use of
+ *     a configuration builds its tables with blocking copies
+ *     (tests/test_gpu_streams.py).
  *   - placement of the `*_dev` buffers: any pointer aligned to its element type
  *     (float: 4 bytes, double and complex64: 8, complex128: 16) is valid -- no
  *     entry point asks for more; a row stride is in elements and >= the row's
@@ -467,7 +474,8 @@ int smx_spectral_flatness_f32_dev(const float *d_s, int64_t lead, int64_t bins, 
  * smx_spectral_contrast_*                  contrast.ml:208-218: audio x [lead; n] -> the magnitude spectrogram -> contrast,
  *                                          clamped
  * smx_spectral_contrast_of_spectrogram_*   fft_size 0: contrast.ml:223-252, the FFT size implied by the bin count, the
- *                                          magnitudes checked (non-negative, no NaN).  fft_size > 0: the body of
+ *                                          magnitudes checked (non-negative, no NaN: the verdict is read back, so the
+ *                                          _dev form synchronises the stream before returning).  fft_size > 0: the body of
  *                                          spectral_contrast_stage (contrast.ml:254-261) for a plan built at that size
  *                                          (errors under that name, magnitudes unchecked; the stage passes clamped 0)
  *

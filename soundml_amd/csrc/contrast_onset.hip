@@ -388,6 +388,9 @@ void contrast_apply_dev(const char *fn, const std::vector<Band> &plan, const Con
   if (check_magnitudes) {         // the reference refuses such a spectrogram: the verdict has to reach the host
     int invalid = 0;
     SMX_HIP_CHECK(hipMemcpyAsync(&invalid, a.invalid, sizeof(int), hipMemcpyDeviceToHost, stream));
+    void *used = scratch.ptr;     // released behind the copy and before the wait: the stream is idle when the verdict is in
+    scratch.ptr = nullptr;
+    SMX_HIP_CHECK(smx::pool_free_async(used, stream));
     SMX_HIP_CHECK(hipStreamSynchronize(stream));
     if (invalid)
       throw InvalidArgument(format(

@@ -173,7 +173,7 @@ void griffin_lim_dev(const smx_stft_config &c, const void *d_s, int elem_bytes, 
     griffin_lim_dev(c, s64, 8, lead, bins, frames, n_iter, momentum, p64, has_length, length, o64, stream);
     launch_gl_narrow(o64, (float *)d_out, lead * out_len, stream);
     for (void *ptr : {(void *)s64, (void *)p64, (void *)o64})
-      if (ptr) SMX_HIP_CHECK(hipFreeAsync(ptr, stream));
+      if (ptr) SMX_HIP_CHECK(smx::pool_free_async(ptr, stream));
     return;
   }
   const int z_bytes = 2 * elem_bytes;
@@ -261,7 +261,7 @@ void griffin_lim_dev(const smx_stft_config &c, const void *d_s, int elem_bytes, 
     }
     synth_fm(cur, old, true, has_length, length, d_out, out_len);
     for (void *ptr : {mag_fm, a_fm, b_fm, c_fm})
-      SMX_HIP_CHECK(hipFreeAsync(ptr, stream));
+      SMX_HIP_CHECK(smx::pool_free_async(ptr, stream));
   } else if (folded) {
     // fused fft-2048 kernels: neither S * angles nor the angles themselves are materialised after the first pass --
     // the synthesis kernel forms S * unit(c_k - beta c_(k-1)) from the two latest rebuilt spectra as it stages them
@@ -304,7 +304,7 @@ void griffin_lim_dev(const smx_stft_config &c, const void *d_s, int elem_bytes, 
     synth(angles, has_length, length, d_out, out_len);
   }
   for (void *ptr : {angles, zbuf, rebuilt, previous, signal})
-    if (ptr) SMX_HIP_CHECK(hipFreeAsync(ptr, stream));
+    if (ptr) SMX_HIP_CHECK(smx::pool_free_async(ptr, stream));
 }
 
 void griffin_lim_host(const smx_stft_config &c, const void *s, int elem_bytes, int64_t lead, int64_t bins,

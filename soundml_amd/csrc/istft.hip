@@ -1040,7 +1040,7 @@ void launch_istft(const IstftJob &job) {
     else SMX_LAUNCH((istft_ola_kernel<float, float>), grid, dim3(256), 0, job.stream, oa);
     SMX_HIP_CHECK(hipGetLastError());
   }
-  SMX_HIP_CHECK(hipFreeAsync(d_y, job.stream));
+  SMX_HIP_CHECK(smx::pool_free_async(d_y, job.stream));
 }
 
 }  // namespace smx

@@ -257,7 +257,7 @@ void mel_spectrogram_dev(const smx_stft_config &sc, const smx_mel_config &mc, co
   job.stft.out = scratch;
   launch_stft(job.stft);
   mel_apply_dev(mc, scratch, in_bytes, lead, sc.bins(), count, d_out, stream);
-  SMX_HIP_CHECK(hipFreeAsync(scratch, stream));
+  SMX_HIP_CHECK(smx::pool_free_async(scratch, stream));
 }
 
 namespace {

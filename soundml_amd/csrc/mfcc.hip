@@ -317,7 +317,7 @@ void run_to_db(const ToDbJob &job) {
   SMX_LAUNCH(to_db_kernel<T>, dim3(blocks), dim3(256), 0, job.stream, (const T *)job.s, (T *)job.out, job.total, (T)job.amin,
                      (T)scale, (T)offset, job.magnitude ? 1 : 0, (const U *)d_key, (T)job.top_db);
   SMX_HIP_CHECK(hipGetLastError());
-  if (d_key) SMX_HIP_CHECK(hipFreeAsync(d_key, job.stream));
+  if (d_key) SMX_HIP_CHECK(smx::pool_free_async(d_key, job.stream));
 }
 
 }  // namespace
@@ -435,7 +435,7 @@ void launch_mfcc(const MfccJob &job) {
     SMX_LAUNCH(mfcc_kernel<float>, grid, dim3(256), 0, job.stream, a);
   }
   SMX_HIP_CHECK(hipGetLastError());
-  SMX_HIP_CHECK(hipFreeAsync(d_max, job.stream));
+  SMX_HIP_CHECK(smx::pool_free_async(d_max, job.stream));
 }
 
 namespace {
@@ -535,7 +535,7 @@ void mfcc_dev(const smx_stft_config &sc, const smx_mel_config &mc, const void *d
   job.out = d_out;
   job.stream = stream;
   launch_mfcc(job);
-  SMX_HIP_CHECK(hipFreeAsync(mel, stream));
+  SMX_HIP_CHECK(smx::pool_free_async(mel, stream));
 }
 
 void mfcc_host(const smx_stft_config &sc, const smx_mel_config &mc, const void *x, int in_bytes, int64_t lead,

@@ -391,6 +391,7 @@ bool launch_stft_complex_fm(const StftJob &job, void *out, int64_t pitch_floats,
 bool fast_path_disabled();                        // env SMX_DISABLE_FAST=1 (tests)
 void init_device_pool();                          // tables.cpp: the library's own stream-ordered pool of the current device
 hipError_t pool_malloc_async(void **ptr, size_t bytes, hipStream_t stream);   // tables.cpp: scratch from that pool
+hipError_t pool_free_async(void *ptr, hipStream_t stream);                    // tables.cpp: back to it, without a runtime call that waits
 void set_scratch_retention(int64_t bytes);        // tables.cpp
 
 // Stft.invert (stft.ml:902-939) on device-resident data
@@ -708,7 +709,7 @@ struct DeviceScratch {
   template <class T> T *as() const { return reinterpret_cast<T *>(ptr); }
   ~DeviceScratch() {
     if (!ptr) return;
-    if (pooled) (void)hipFreeAsync(ptr, stream);
+    if (pooled) (void)pool_free_async(ptr, stream);
     else (void)hipFree(ptr);
   }
 };

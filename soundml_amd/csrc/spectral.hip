@@ -293,8 +293,8 @@ bool launch_spectral(const SpectralJob &job) {
   else dispatch_feature<float>(job.feature, a, job.stream);
   int invalid = 0;
   SMX_HIP_CHECK(hipMemcpyAsync(&invalid, a.invalid, sizeof(int), hipMemcpyDeviceToHost, job.stream));
+  SMX_HIP_CHECK(smx::pool_free_async(scratch, job.stream));   // behind the copy and before the wait: the stream is idle when the verdict is in
   SMX_HIP_CHECK(hipStreamSynchronize(job.stream));
-  SMX_HIP_CHECK(hipFreeAsync(scratch, job.stream));
   return invalid == 0;
 }
 
@@ -328,7 +328,7 @@ void launch_chroma(const ChromaJob &job) {
     SMX_LAUNCH(chroma_normalise_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, job.stream, a);
   }
   SMX_HIP_CHECK(hipGetLastError());
-  SMX_HIP_CHECK(hipFreeAsync(a.raw, job.stream));
+  SMX_HIP_CHECK(smx::pool_free_async(a.raw, job.stream));
 }
 
 }  // namespace smx
@@ -526,7 +526,7 @@ void chroma_stft_dev(const smx_stft_config &sc, const smx_chroma_config &cc, con
   SMX_HIP_CHECK(smx::pool_malloc_async(&spec, (size_t)lead * (size_t)sc.bins() * (size_t)count * (size_t)in_bytes, stream));
   stft_range_dev(sc, d_x, in_bytes, lead, n, x_stride, 0, count, OUT_POWER, power, spec, stream);
   chroma_apply_dev(cc, spec, in_bytes, lead, sc.bins(), count, norm, norm_p, d_out, stream);
-  SMX_HIP_CHECK(hipFreeAsync(spec, stream));
+  SMX_HIP_CHECK(smx::pool_free_async(spec, stream));
 }
 
 void chroma_stft_host(const smx_stft_config &sc, const smx_chroma_config &cc, const void *x, int in_bytes,

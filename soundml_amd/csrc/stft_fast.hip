@@ -615,7 +615,7 @@ void launch_border(const StftJob &job, const FastTarget &tg, int64_t pa, int64_t
   const GatherSpan span = alloc_strip(job, pa, pb);
   gather_strips(job, span, span, 1);
   launch_interior(job, tg, span.out, span.len, span.out_stride, 0, 0, pb - pa, tg.out_offset + (pa - job.p0), /*strip=*/true);
-  SMX_HIP_CHECK(hipFreeAsync(span.out, job.stream));
+  SMX_HIP_CHECK(smx::pool_free_async(span.out, job.stream));
 }
 
 bool fast_eligible(const StftJob &job, bool power_face = false) {
@@ -694,7 +694,7 @@ void launch_ranges(const StftJob &job, const FastTarget &tg) {
   gather_strips(job, left, right, 2);
   launch_interior(job, folded, x, job.n, job.x_stride, job.left, p0, p1 - p0, tg.out_offset);
   for (float *sp : {left.out, right.out})
-    if (sp) SMX_HIP_CHECK(hipFreeAsync(sp, job.stream));
+    if (sp) SMX_HIP_CHECK(smx::pool_free_async(sp, job.stream));
 }
 
 }  // namespace

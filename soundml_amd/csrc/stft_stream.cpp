@@ -215,7 +215,7 @@ int64_t process(smx_stft_kernel &k, const void *extra, int64_t extra_stride, int
     SMX_HIP_CHECK(smx::pool_malloc_async(&tmp, (size_t)k.channels * (size_t)keep * es, stream));
     rows_copy(tmp, keep, 0, k.d_stream, k.cap, next_start, keep, k.channels, es, stream);
     rows_copy(k.d_stream, k.cap, 0, tmp, keep, 0, keep, k.channels, es, stream);
-    SMX_HIP_CHECK(hipFreeAsync(tmp, stream));
+    SMX_HIP_CHECK(smx::pool_free_async(tmp, stream));
     k.pending_len = keep;
   }
   return count;
@@ -241,7 +241,7 @@ void update_tail(smx_stft_kernel &k, const void *chunk, int64_t chunk_stride, in
     SMX_HIP_CHECK(smx::pool_malloc_async(&tmp, (size_t)k.channels * (size_t)kept_old * es, stream));
     rows_copy(tmp, kept_old, 0, k.d_tail, keep, start, kept_old, k.channels, es, stream);
     rows_copy(k.d_tail, keep, 0, tmp, kept_old, 0, kept_old, k.channels, es, stream);
-    SMX_HIP_CHECK(hipFreeAsync(tmp, stream));
+    SMX_HIP_CHECK(smx::pool_free_async(tmp, stream));
   }
   const int64_t old = kept_old > 0 ? kept_old : 0;
   // (start >= tail_len cannot happen: then m >= keep)
@@ -268,7 +268,7 @@ int64_t install(smx_stft_kernel &k, const void *x, int64_t x_stride, int64_t n, 
   stream_pad(k, both, bl, k.left, x, x_stride, n, 0, stream);
   rows_copy(both, bl, k.left, x, x_stride, 0, n, k.channels, es, stream);
   const int64_t emitted = process(k, both, bl, 0, bl, out, stream);
-  SMX_HIP_CHECK(hipFreeAsync(both, stream));
+  SMX_HIP_CHECK(smx::pool_free_async(both, stream));
   return emitted;
 }
 
@@ -290,7 +290,7 @@ int64_t step_core(smx_stft_kernel &k, const void *chunk, int64_t chunk_stride, i
       rows_copy(x, n, 0, k.d_prelude, k.prelude_cap, 0, k.prelude_len, k.channels, es, stream);
       rows_copy(x, n, k.prelude_len, chunk, chunk_stride, 0, m, k.channels, es, stream);
       const int64_t emitted = install(k, x, n, n, out, stream);
-      SMX_HIP_CHECK(hipFreeAsync(x, stream));
+      SMX_HIP_CHECK(smx::pool_free_async(x, stream));
       return emitted;
     }
     if (n > k.prelude_cap) {   // below the install threshold: at most left samples ever wait here
@@ -332,7 +332,7 @@ int64_t flush_core(smx_stft_kernel &k, const StreamOut &out, hipStream_t stream)
       k.started = true;
       k.prelude_len = 0;
       emitted = process(k, padded, pl, 0, pl, out, stream);
-      SMX_HIP_CHECK(hipFreeAsync(padded, stream));
+      SMX_HIP_CHECK(smx::pool_free_async(padded, stream));
     }
   } else if (k.right > 0) {
     const int64_t r = k.right;
@@ -345,7 +345,7 @@ int64_t flush_core(smx_stft_kernel &k, const StreamOut &out, hipStream_t stream)
       const int64_t dropped = k.skip;
       k.skip = 0;
       emitted = process(k, rp, r, dropped, r - dropped, out, stream);
-      SMX_HIP_CHECK(hipFreeAsync(rp, stream));
+      SMX_HIP_CHECK(smx::pool_free_async(rp, stream));
     }
   }
   k.pending_len = 0;
@@ -556,7 +556,7 @@ int64_t synth_emit(smx_stft_synthesis &s, int64_t frames_local, int64_t nq, int6
                            carry_next, (int)s.elem(), stream);
   if (keep > 0) {
     SMX_HIP_CHECK(hipMemcpyAsync(s.d_carry, carry_next, (size_t)s.channels * (size_t)s.hold * (size_t)s.elem(), hipMemcpyDeviceToDevice, stream));
-    SMX_HIP_CHECK(hipFreeAsync(carry_next, stream));
+    SMX_HIP_CHECK(smx::pool_free_async(carry_next, stream));
   }
   s.carry_len = keep;
   return emit;

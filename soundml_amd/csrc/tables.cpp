@@ -83,16 +83,20 @@ static std::mutex g_pool_mutex;
 static std::map<int, bool> g_pool_done;
 static int64_t g_pool_bytes = -1;   // < 0: the default
 
+static void release_idle_locked();
+
 void set_scratch_retention(int64_t bytes) {
   std::lock_guard<std::mutex> lock(g_pool_mutex);
   g_pool_bytes = bytes;
   g_pool_done.clear();
+  release_idle_locked();   // what is held idle was kept under the old threshold
 }
 
 // The library's OWN stream-ordered pool, one per device (never the process-wide default pool, whose release threshold an
 // embedding application may rely on): scratch arrays come from it and go back to it, and it keeps up to `threshold`
 // bytes of freed scratch for the next call instead of returning them to the driver at every synchronisation.
 static std::map<int, hipMemPool_t> g_pools;
+static std::map<int, uint64_t> g_threshold;   // the retention of each device, as set on its pool
 
 static uint64_t pool_threshold_locked() {
   if (g_pool_bytes >= 0) return (uint64_t)g_pool_bytes;
@@ -115,9 +119,10 @@ static hipMemPool_t device_pool_locked(int device) {
     it = g_pools.emplace(device, pool).first;
     g_pool_done[device] = false;
   }
-  if (it->second && !g_pool_done[device]) {
+  if (!g_pool_done[device]) {
     uint64_t threshold = pool_threshold_locked();
-    (void)hipMemPoolSetAttribute(it->second, hipMemPoolAttrReleaseThreshold, &threshold);
+    g_threshold[device] = threshold;
+    if (it->second) (void)hipMemPoolSetAttribute(it->second, hipMemPoolAttrReleaseThreshold, &threshold);
     g_pool_done[device] = true;
   }
   return it->second;
@@ -130,16 +135,77 @@ void init_device_pool() {
   (void)device_pool_locked(device);
 }
 
+// Freed scratch waits here, per device and stream, for the next request on the SAME stream: stream order alone makes that reuse
+// safe, and no runtime call is made.  The runtime's own free is kept off the device paths because it waits: hipFreeAsync of a block
+// that the pool handed out again on the stream of its previous free blocks the host until that earlier free has run on the device,
+// so two calls in a row on a busy stream (or two scratch arrays of one size in one call) would synchronise the caller's stream
+// (tests/test_gpu_streams.py).  Idle blocks count against the retention threshold; past it a block goes back to the runtime.
+struct IdleBlock {
+  void *ptr;
+  size_t bytes;
+};
+static std::map<std::pair<int, hipStream_t>, std::vector<IdleBlock>> g_idle;
+static std::map<void *, size_t> g_scratch_bytes;   // every block handed out or idle -> its size
+static uint64_t g_idle_bytes = 0;
+
+static void release_idle_locked() {   // everything idle goes back to the driver (hipFree waits for the device: setters and retries only)
+  for (auto &kv : g_idle)
+    for (IdleBlock &b : kv.second) {
+      g_scratch_bytes.erase(b.ptr);
+      (void)hipFree(b.ptr);
+    }
+  g_idle.clear();
+  g_idle_bytes = 0;
+}
+
 hipError_t pool_malloc_async(void **ptr, size_t bytes, hipStream_t stream) {
   int device = 0;
   hipError_t e = hipGetDevice(&device);
   if (e != hipSuccess) return e;
-  hipMemPool_t pool = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(g_pool_mutex);
-    pool = device_pool_locked(device);
+  bytes = (bytes + 255) / 256 * 256;
+  if (bytes == 0) bytes = 256;
+  std::lock_guard<std::mutex> lock(g_pool_mutex);
+  hipMemPool_t pool = device_pool_locked(device);
+  auto it = g_idle.find(std::make_pair(device, stream));
+  if (it != g_idle.end()) {
+    std::vector<IdleBlock> &idle = it->second;
+    size_t best = idle.size();
+    for (size_t i = 0; i < idle.size(); ++i)   // the smallest block that fits and is at most twice the request
+      if (idle[i].bytes >= bytes && idle[i].bytes <= 2 * bytes && (best == idle.size() || idle[i].bytes < idle[best].bytes)) best = i;
+    if (best != idle.size()) {
+      *ptr = idle[best].ptr;
+      g_idle_bytes -= idle[best].bytes;
+      idle.erase(idle.begin() + (std::ptrdiff_t)best);
+      return hipSuccess;
+    }
   }
-  return pool ? hipMallocFromPoolAsync(ptr, bytes, pool, stream) : hipMallocAsync(ptr, bytes, stream);
+  e = pool ? hipMallocFromPoolAsync(ptr, bytes, pool, stream) : hipMallocAsync(ptr, bytes, stream);
+  if (e != hipSuccess && g_idle_bytes > 0) {   // out of memory with scratch held idle: give it back and ask once more
+    (void)hipGetLastError();
+    release_idle_locked();
+    e = pool ? hipMallocFromPoolAsync(ptr, bytes, pool, stream) : hipMallocAsync(ptr, bytes, stream);
+  }
+  if (e == hipSuccess) g_scratch_bytes[*ptr] = bytes;
+  return e;
+}
+
+hipError_t pool_free_async(void *ptr, hipStream_t stream) {
+  if (!ptr) return hipSuccess;
+  int device = 0;
+  hipError_t e = hipGetDevice(&device);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(g_pool_mutex);
+  auto known = g_scratch_bytes.find(ptr);
+  if (known == g_scratch_bytes.end()) return hipFreeAsync(ptr, stream);
+  const size_t bytes = known->second;
+  (void)device_pool_locked(device);
+  if (g_idle_bytes + bytes > g_threshold[device]) {   // past the retention: back to the runtime, as before
+    g_scratch_bytes.erase(known);
+    return hipFreeAsync(ptr, stream);
+  }
+  g_idle[std::make_pair(device, stream)].push_back(IdleBlock{ptr, bytes});
+  g_idle_bytes += bytes;
+  return hipSuccess;
 }
 
 // Compute units of the current device: the size of every persistent grid.  Cached per device ordinal in atomics (rounds 1-5 kept

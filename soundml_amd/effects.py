@@ -26,6 +26,23 @@ from ._lib import check, lib
 from ._tensor import Batch, is_device, is_torch, out_ptr, prod, torch
 
 _PHASE = {"independent": 0, "locked": 1}
+_RESAMPLERS = {}    # (num, den, quality) -> Resample.Config: its filter bank is uploaded once, and freeing one waits for the device
+
+
+def _resampler(num, den, quality):
+    """The resampler of a ratio, kept for the next call (a config built per call would upload its bank and free it again,
+    which synchronises the device); an unhashable quality gets a config of its own."""
+    try:
+        key = (num, den, quality if isinstance(quality, str) else tuple(quality))
+        hash(key)
+    except TypeError:
+        return _ResampleConfig.create(num, den, quality)
+    config = _RESAMPLERS.get(key)
+    if config is None:
+        if len(_RESAMPLERS) >= 64:
+            _RESAMPLERS.pop(next(iter(_RESAMPLERS)))
+        config = _RESAMPLERS[key] = _ResampleConfig.create(num, den, quality)
+    return config
 
 
 def _g(v: float) -> str:
@@ -155,6 +172,6 @@ def pitch_shift(c, x, ratio, phase: str = "independent", quality="high"):
     mode = _phase(fn, phase)
     # time_stretch's conditions (Stft.invert's among them) come before the resampler's, as in the reference: the checks alone, no clip
     check(lib.smx_time_stretch_f32(c._h, None, 0, int(x.shape[-1]), float(den) / float(num), mode, None))
-    resampler = _ResampleConfig.create(num, den, quality)
+    resampler = _resampler(num, den, quality)
     return _signal_call(fn, x, int(x.shape[-1]), (lib.smx_pitch_shift_f32, lib.smx_pitch_shift_f64), lib.smx_pitch_shift_f32_dev,
                         (c._h, resampler._h, mode), ())
