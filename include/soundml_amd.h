@@ -1307,6 +1307,77 @@ int smx_resample_stream_step_f32_dev(smx_resample_stream *k, const float *d_x, i
                                      int64_t y_stride, int64_t *n_out, void *stream);
 int smx_resample_stream_flush_f32_dev(smx_resample_stream *k, float *d_y, int64_t y_stride, int64_t *n_out, void *stream);
 
+/* ---- Iir: recursive filters as cascaded second-order sections (scipy.signal.sosfilt / sosfilt_zi / sosfiltfilt; the
+ * reference lists "IIR/FIR filtering" as planned and has no such module) -----------------------------------------------------
+ * sos is [S; 6] float64 with rows b0 b1 b2 a0 a1 a2, 1 <= S <= smx_iir_max_sections() = 8, every a0 exactly 1.0, all finite.
+ * Audio x [lead; n] -> y [lead; n].  One step of the cascade on a sample u, in float64, every product and every sum rounded
+ * on its own (no fused operation), for k = 0 .. S-1 in turn:
+ *     y = b0 u + z[k][0];   z[k][0] = (b1 u - a1 y) + z[k][1];   z[k][1] = b2 u - a2 y;   u = y
+ * Run serially from a zero state this is sosfilt's float64 output bit for bit.  A state is [S; 2] float64, z[k][0], z[k][1].
+ *
+ * The stated order, shared bit for bit by both kernels, the host faces and the stream kernel.  Time is cut
+ * into blocks of B = smx_iir_block() = 256 samples counted from the first sample of the call (of the stream since reset).
+ * s_b is the state entering block b, s_0 = zi or zero.  The outputs of block b are the serial cascade run from s_b over the
+ * block's samples; w_b is the end state of the same cascade over the same samples from a ZERO state;
+ *     s_{b+1}[i] = (((M[i][0] s_b[0] + M[i][1] s_b[1]) + M[i][2] s_b[2]) + ...) + w_b[i]       ascending j, w_b last
+ * with M [2S; 2S] built on the host (smx_iir_matrix, row-major): column i is the end state of B zero-input steps of the
+ * cascade from the unit state e_i.  Outputs are rounded once, to the dtype of the input.  The state handed back (zf) is the
+ * running state after the last sample: s_{b+1} where the call ends on a block edge.  A leading slice of a batch, both kernels
+ * (SMX_DISABLE_FAST=1 forces the general one) and every chunking of the stream kernel give the same bits; a call continued
+ * from another call's zf restarts the block grid and agrees to rounding only.
+ *
+ *   smx_iir_zi        the unit-step steady state in closed form, [S; 2]: per section g = (b0 + b1 + b2) / (1 + a1 + a2),
+ *                     z[k][0] = g - b0, z[k][1] = b2 - a2 g, both times the product of the earlier sections' g
+ *                     (sosfilt_zi to rounding).  A section with 1 + a1 + a2 == 0 is refused.
+ *   smx_iir_apply_*   zi: NULL (zero state), [S; 2] (zi_rows 0) or [lead; S; 2] (zi_rows 1); zf: NULL or [lead; S; 2].
+ *                     n = 0 hands zi back as zf.
+ *   smx_iir_filtfilt_*  sosfiltfilt with its defaults: odd extension by padlen = 3 (2 S + 1 - min(#rows with b2 == 0,
+ *                     #rows with a2 == 0)) samples on each side, 2 x[0] - x[padlen - i] and 2 x[n-1] - x[n-2-k] taken in
+ *                     float64; a forward pass from zi times the extended signal's first sample; the float64 result reversed;
+ *                     a second pass from zi times ITS first sample; reversed again, trimmed, rounded once.  Each pass's block
+ *                     grid starts at that pass's first sample.  n <= padlen is refused.
+ *   smx_iir_kernel_*  Iir.Kernel.{prepare, step, flush, reset}: 6 S doubles per channel stay on the device (s_b, the partial
+ *                     w, the running state); the position inside the block is a host integer.  A step takes [channels; m]
+ *                     and returns [channels; m] (latency zero) and may begin and end anywhere inside a block; the
+ *                     concatenated steps equal smx_iir_apply_* of the whole signal bit for bit.  flush emits nothing and
+ *                     drains the kernel: a step after it is refused until reset.  The kernel shares the configuration's
+ *                     tables and may outlive the handle.
+ *
+ * The device-resident forms end in `_card_f32` (the placement and stream suites keep closed tables of the other endings; these
+ * have tables and laws of their own: tests/test_gpu_placement_iir.py, tests/test_gpu_streams_iir.py) and take the stream
+ * directly after the handle.  Rows of d_x lie x_stride >= n apart, results are dense.  smx_iir_apply_card_f32 takes the per-call
+ * state zi from HOST memory (it travels with the launch) and the per-channel one, d_zi_rows, from device memory; at most one
+ * of the two.  Everything is enqueued on `stream`; nothing synchronises it. */
+typedef struct smx_iir smx_iir;
+typedef struct smx_iir_kernel smx_iir_kernel;
+int smx_iir_create(const double *sos, int64_t sections, smx_iir **out);
+void smx_iir_destroy(smx_iir *c);
+int64_t smx_iir_block(void);
+int64_t smx_iir_span_blocks(void);       /* blocks a wave of the block route owns: 64 */
+int64_t smx_iir_max_sections(void);
+int64_t smx_iir_sections(const smx_iir *c);
+int64_t smx_iir_padlen(const smx_iir *c);
+int smx_iir_matrix(const smx_iir *c, double *m /* [2 S; 2 S] */);
+int smx_iir_zi(const smx_iir *c, double *zi /* [S; 2] */);
+int smx_iir_apply_f32(const smx_iir *c, const float *x, int64_t lead, int64_t n, const double *zi, int zi_rows, float *out,
+                      double *zf);
+int smx_iir_apply_f64(const smx_iir *c, const double *x, int64_t lead, int64_t n, const double *zi, int zi_rows, double *out,
+                      double *zf);
+int smx_iir_apply_card_f32(const smx_iir *c, void *stream, const float *d_x, int64_t lead, int64_t n, int64_t x_stride,
+                           const double *zi, const double *d_zi_rows, float *d_out, double *d_zf);
+int smx_iir_filtfilt_f32(const smx_iir *c, const float *x, int64_t lead, int64_t n, float *out);
+int smx_iir_filtfilt_f64(const smx_iir *c, const double *x, int64_t lead, int64_t n, double *out);
+int smx_iir_filtfilt_card_f32(const smx_iir *c, void *stream, const float *d_x, int64_t lead, int64_t n, int64_t x_stride,
+                              float *d_out);
+int smx_iir_kernel_prepare(const smx_iir *c, int64_t channels, smx_iir_kernel **out);
+void smx_iir_kernel_destroy(smx_iir_kernel *k);
+int smx_iir_kernel_reset(smx_iir_kernel *k);
+int smx_iir_kernel_flush(smx_iir_kernel *k);
+int64_t smx_iir_kernel_position(const smx_iir_kernel *k);   /* samples per channel since reset */
+int smx_iir_kernel_step_f32(smx_iir_kernel *k, const float *x, int64_t m, float *out);
+int smx_iir_kernel_step_f64(smx_iir_kernel *k, const double *x, int64_t m, double *out);
+int smx_iir_kernel_step_card_f32(smx_iir_kernel *k, void *stream, const float *d_x, int64_t m, int64_t x_stride, float *d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -406,6 +406,29 @@ SIGNATURES = {
     "smx_fir_plan_block": (i64, [vp]),
     "smx_fir_apply_f32": (cint, [vp, vp, i64, i64, vp]),
     "smx_fir_apply_f32_dev": (cint, [vp, vp, i64, i64, i64, vp, i64, vp]),
+    "smx_iir_create": (cint, [vp, i64, C.POINTER(vp)]),
+    "smx_iir_destroy": (None, [vp]),
+    "smx_iir_block": (i64, []),
+    "smx_iir_span_blocks": (i64, []),
+    "smx_iir_max_sections": (i64, []),
+    "smx_iir_sections": (i64, [vp]),
+    "smx_iir_padlen": (i64, [vp]),
+    "smx_iir_matrix": (cint, [vp, vp]),
+    "smx_iir_zi": (cint, [vp, vp]),
+    "smx_iir_apply_f32": (cint, [vp, vp, i64, i64, vp, cint, vp, vp]),
+    "smx_iir_apply_f64": (cint, [vp, vp, i64, i64, vp, cint, vp, vp]),
+    "smx_iir_apply_card_f32": (cint, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp]),
+    "smx_iir_filtfilt_f32": (cint, [vp, vp, i64, i64, vp]),
+    "smx_iir_filtfilt_f64": (cint, [vp, vp, i64, i64, vp]),
+    "smx_iir_filtfilt_card_f32": (cint, [vp, vp, vp, i64, i64, i64, vp]),
+    "smx_iir_kernel_prepare": (cint, [vp, i64, C.POINTER(vp)]),
+    "smx_iir_kernel_destroy": (None, [vp]),
+    "smx_iir_kernel_reset": (cint, [vp]),
+    "smx_iir_kernel_flush": (cint, [vp]),
+    "smx_iir_kernel_position": (i64, [vp]),
+    "smx_iir_kernel_step_f32": (cint, [vp, vp, i64, vp]),
+    "smx_iir_kernel_step_f64": (cint, [vp, vp, i64, vp]),
+    "smx_iir_kernel_step_card_f32": (cint, [vp, vp, vp, i64, i64, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
