@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, prod, refuse_device_float64
 
 NORM_NONE, NORM_INF, NORM_P = 0, 1, 2
 
@@ -103,18 +103,10 @@ def apply(c: Config, s, norm="inf"):
     lead = prod(lead_shape)
     if bins != c.bins:
         check(lib.smx_chroma_apply_f32(c._h, None, lead, bins, frames, kind, p, None))
-    out = b.empty(lead_shape + (c.n_chroma, frames))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("apply: device-resident float64 spectrograms are not supported; pass a host array")
-        if out.numel() > 0:
-            out.zero_()
-        with b.device_guard():
-            check(lib.smx_chroma_apply_f32_dev(c._h, b.ptr(), lead, bins, frames, kind, p, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_chroma_apply_f32 if b.bytes == 4 else lib.smx_chroma_apply_f64
-    check(fn(c._h, b.ptr(), lead, bins, frames, kind, p, out_ptr(out)))
-    return b.wrap(out)
+    refuse_device_float64("apply", b, "spectrograms are")
+    args = (c._h, b.ptr(), lead, bins, frames, kind, p, OUT)
+    return b.run((lib.smx_chroma_apply_f32, lib.smx_chroma_apply_f64), args, lib.smx_chroma_apply_f32_dev, args + (STREAM,),
+                 lead_shape + (c.n_chroma, frames), prefill=True)
 
 
 def cqt_projection(dtype, c, n_chroma: int = 12) -> np.ndarray:
@@ -142,14 +134,7 @@ def of_cqt(c, s, n_chroma: int = 12, norm="inf"):
     lead = prod(lead_shape)
     if bins != c.n_bins:
         check(lib.smx_chroma_of_cqt_f32(c._h, None, lead, bins, frames, n_chroma, kind, p, None))
-    out = b.empty(lead_shape + (n_chroma, frames))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("of_cqt: device-resident float64 spectrograms are not supported; pass a host array")
-        with b.device_guard():
-            check(lib.smx_chroma_of_cqt_f32_dev(c._h, b.ptr(), lead, bins, frames, n_chroma, kind, p,
-                                                out_ptr(out) if out.numel() else None, b.stream()))
-        return out
-    fn = lib.smx_chroma_of_cqt_f32 if b.bytes == 4 else lib.smx_chroma_of_cqt_f64
-    check(fn(c._h, b.ptr(), lead, bins, frames, n_chroma, kind, p, out_ptr(out) if out.size else None))
-    return b.wrap(out)
+    refuse_device_float64("of_cqt", b, "spectrograms are")
+    args = (c._h, b.ptr(), lead, bins, frames, n_chroma, kind, p, OUT)
+    return b.run((lib.smx_chroma_of_cqt_f32, lib.smx_chroma_of_cqt_f64), args, lib.smx_chroma_of_cqt_f32_dev, args + (STREAM,),
+                 lead_shape + (n_chroma, frames), null_empty=True)

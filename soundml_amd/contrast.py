@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, Stateless, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, Stateless, prod, refuse_device_float64
 from . import stft as Stft
 
 
@@ -34,11 +34,6 @@ def _params(n_bands, f_min, quantile, linear, sample_rate):
     return int(n_bands), float(f_min), float(quantile), 1 if linear else 0, int(sample_rate)
 
 
-def _refuse_device_float64(op, b):
-    if b.device and b.bytes != 4:
-        raise _lib.Failure("%s: device-resident float64 spectrograms are not supported; pass a host array" % op)
-
-
 def spectral_contrast(stft_config, x, sample_rate: int, n_bands: int = 6, f_min: float = 200.0, quantile: float = 0.02,
                       linear: bool = False):
     """``Soundml.spectral_contrast stft ?n_bands ?f_min ?quantile ?linear ~sample_rate x`` (contrast.ml:208-218)."""
@@ -49,16 +44,10 @@ def spectral_contrast(stft_config, x, sample_rate: int, n_bands: int = 6, f_min:
     n = int(b.shape[-1])
     lead_shape = b.shape[:-1]
     lead = prod(lead_shape)
-    out = b.empty(lead_shape + (q[0] + 1, Stft.frames(stft_config, n)))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("spectral_contrast: device-resident float64 audio is not supported; pass a host array")
-        with b.device_guard():
-            check(lib.smx_spectral_contrast_dev_f32(stft_config._h, b.ptr(), lead, n, n, *q, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_spectral_contrast_f32 if b.bytes == 4 else lib.smx_spectral_contrast_f64
-    check(fn(stft_config._h, b.ptr(), lead, n, *q, out_ptr(out)))
-    return b.wrap(out)
+    shape = lead_shape + (q[0] + 1, Stft.frames(stft_config, n))
+    refuse_device_float64("spectral_contrast", b)
+    return b.run((lib.smx_spectral_contrast_f32, lib.smx_spectral_contrast_f64), (stft_config._h, b.ptr(), lead, n, *q, OUT),
+                 lib.smx_spectral_contrast_dev_f32, (stft_config._h, b.ptr(), lead, n, n, *q, OUT, STREAM), shape)
 
 
 def _of_spectrogram(op, s, fft_size, q, clamped):
@@ -71,17 +60,12 @@ def _of_spectrogram(op, s, fft_size, q, clamped):
     args = (lead, bins, frames, fft_size) + q + (1 if clamped else 0,)
     # what does not read the data, worded by the ABI before anything is allocated (no clips: no device work)
     check(lib.smx_spectral_contrast_of_spectrogram_f32(None, 0, bins, 0, *args[3:], None))
-    if lead == 0 or bins == 0 or frames == 0:
-        return b.wrap(b.empty(lead_shape + (q[0] + 1, frames)))
-    _refuse_device_float64(op, b)
-    out = b.empty(lead_shape + (q[0] + 1, frames))
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_spectral_contrast_of_spectrogram_dev_f32(b.ptr(), *args, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_spectral_contrast_of_spectrogram_f32 if b.bytes == 4 else lib.smx_spectral_contrast_of_spectrogram_f64
-    check(fn(b.ptr(), *args, out_ptr(out)))
-    return b.wrap(out)
+    skip = lead == 0 or bins == 0 or frames == 0
+    if not skip:
+        refuse_device_float64(op, b, "spectrograms are")
+    return b.run((lib.smx_spectral_contrast_of_spectrogram_f32, lib.smx_spectral_contrast_of_spectrogram_f64), (b.ptr(), *args, OUT),
+                 lib.smx_spectral_contrast_of_spectrogram_dev_f32, (b.ptr(), *args, OUT, STREAM), lead_shape + (q[0] + 1, frames),
+                 skip=skip, empty="uninitialised")
 
 
 def spectral_contrast_of_spectrogram(s, sample_rate: int, n_bands: int = 6, f_min: float = 200.0, quantile: float = 0.02,

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, prod
 from .features import amplitude_to_db, power_to_db  # noqa: F401
 
 
@@ -23,14 +23,9 @@ def _from_db(which, db, reference):
         db = np.asarray(db)
     b = Batch(db, which, min_rank=0)
     total = prod(b.shape)
-    out = b.empty(b.shape)
-    sfx = "f32" if b.bytes == 4 else "f64"
-    if b.device:
-        with b.device_guard():
-            check(getattr(lib, "smx_%s_%s_dev" % (which, sfx))(b.ptr(), total, float(reference), out_ptr(out), b.stream()))
-        return out
-    check(getattr(lib, "smx_%s_%s" % (which, sfx))(b.ptr(), total, float(reference), out_ptr(out)))
-    return b.wrap(out)
+    entries = [getattr(lib, "smx_%s_%s" % (which, sfx)) for sfx in ("f32", "f64", "f32_dev", "f64_dev")]
+    args = (b.ptr(), total, float(reference), OUT)
+    return b.run(entries[:2], args, entries[2:], args + (STREAM,), b.shape)
 
 
 def db_to_power(db, reference: float = 1.0):

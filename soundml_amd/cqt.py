@@ -32,7 +32,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, out_ptr, prod
 
 C1 = 32.70319566257483
 _GAMMA = {"constant_q": 0, "erb": 1}
@@ -178,32 +178,22 @@ def _batch(fn, x):
     return b
 
 
-def _run(fn, c, x, complex_, host_call, dev_call):
+def _run(fn, c, x, complex_, host, device, params):
     b = _batch(fn, x)
     lead_shape, n = b.shape[:-1], int(b.shape[-1])
     lead = prod(lead_shape)
-    out = b.empty(lead_shape + (c.n_bins, frames(c, n)), complex_=complex_)
-    if b.device:
-        with b.device_guard():
-            check(dev_call(b.ptr(), lead, n, max(n, 1), out_ptr(out) if out.numel() else None, b.stream()))
-        return out
-    check(host_call(b.ptr(), lead, n, out_ptr(out) if out.size else None))
-    return b.wrap(out)
+    return b.run(host, (c._h, b.ptr(), lead, n, *params, OUT), device, (c._h, b.ptr(), lead, n, max(n, 1), *params, OUT, STREAM),
+                 lead_shape + (c.n_bins, frames(c, n)), complex_=complex_, null_empty=True)
 
 
 def transform(c: Config, x):
     """``Cqt.transform cdtype c x`` (cqt.mli:285-303): ``[...; n]`` float32 -> ``[...; n_bins; frames]`` complex64."""
-    return _run("transform", c, x, True,
-                lambda x_, lead, n, out: lib.smx_cqt_transform_f32(c._h, x_, lead, n, out),
-                lambda x_, lead, n, stride, out, stream: lib.smx_cqt_transform_f32_dev(c._h, x_, lead, n, stride, out, stream))
+    return _run("transform", c, x, True, lib.smx_cqt_transform_f32, lib.smx_cqt_transform_f32_dev, ())
 
 
 def power_spectrum(c: Config, x, power: float = 2.0):
     """``Cqt.power_spectrum ?power c x`` (cqt.mli:305-315): ``|transform c x| ^ power`` in float32, ``[...; n_bins; frames]``."""
-    power = float(power)
-    return _run("power_spectrum", c, x, False,
-                lambda x_, lead, n, out: lib.smx_cqt_power_spectrum_f32(c._h, x_, lead, n, power, out),
-                lambda x_, lead, n, stride, out, stream: lib.smx_cqt_power_spectrum_f32_dev(c._h, x_, lead, n, stride, power, out, stream))
+    return _run("power_spectrum", c, x, False, lib.smx_cqt_power_spectrum_f32, lib.smx_cqt_power_spectrum_f32_dev, (float(power),))
 
 
 # ---- Cqt.Kernel: the streaming transform (cqt.mli:317-413) ------------------------------------------------------------------

@@ -23,8 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, is_device, is_torch, out_ptr, prod
-from .energy import _refuse_device_float64, _zeros
+from ._tensor import OUT, STREAM, Batch, is_device, is_torch, out_ptr, prod, refuse_device_float64
 
 
 def _caps():
@@ -113,24 +112,15 @@ def nmf(V, n_components: int, n_iter: int = 100, beta: str = "frobenius", W0=Non
     wide = str(getattr(V, "dtype", "")).endswith("float64")
     check((lib.smx_nmf_f64 if wide else lib.smx_nmf_f32)(None, None, None, 0, F, T, K, n_iter, code, None, None))
     b = _Spectrogram(V, name)
-    _refuse_device_float64(name, b, "spectrograms are")
+    refuse_device_float64(name, b, "spectrograms are")
     lead = b.lead_shape
     if W0 is None or H0 is None:
         w, h = initial(lead, F, T, K, seed)
         W0, H0 = (w if W0 is None else W0), (h if H0 is None else H0)
     W0, H0 = _factor(name, b, W0, lead + (F, K), "W0"), _factor(name, b, H0, lead + (K, T), "H0")
-    if b.clips == 0:
-        return _zeros(b, lead + (F, K)), _zeros(b, lead + (K, T))
-    W, H = b.empty(lead + (F, K)), b.empty(lead + (K, T))
-    if b.device:
-        v, vs, vp = b.placed()
-        with b.device_guard():
-            check(lib.smx_nmf_vram_f32(v, vs, vp, _ptr(W0), F * K, _ptr(H0), K * T, b.clips, F, T, K, n_iter, code, _ptr(W), F * K, _ptr(H), K * T,
-                                       b.stream()))
-        return W, H
-    fn = lib.smx_nmf_f32 if b.bytes == 4 else lib.smx_nmf_f64
-    check(fn(b.ptr(), _ptr(W0), _ptr(H0), b.clips, F, T, K, n_iter, code, _ptr(W), _ptr(H)))
-    return b.wrap(W), b.wrap(H)
+    return b.run((lib.smx_nmf_f32, lib.smx_nmf_f64), (b.ptr(), _ptr(W0), _ptr(H0), b.clips, F, T, K, n_iter, code, OUT, OUT),
+                 lib.smx_nmf_vram_f32, (*b.placed(), _ptr(W0), F * K, _ptr(H0), K * T, b.clips, F, T, K, n_iter, code, OUT, F * K, OUT, K * T, STREAM),
+                 [lead + (F, K), lead + (K, T)], skip=b.clips == 0)
 
 
 def nmf_activations(V, W, n_iter: int = 100, beta: str = "frobenius", H0=None, seed: int = 0):
@@ -144,7 +134,7 @@ def nmf_activations(V, W, n_iter: int = 100, beta: str = "frobenius", H0=None, s
     wide = str(getattr(V, "dtype", "")).endswith("float64")
     check((lib.smx_nmf_activations_f64 if wide else lib.smx_nmf_activations_f32)(None, None, None, 0, F, T, K, n_iter, code, None))
     b = _Spectrogram(V, name)
-    _refuse_device_float64(name, b, "spectrograms are")
+    refuse_device_float64(name, b, "spectrograms are")
     lead = b.lead_shape
     shared = len(lead) > 0 and tuple(W.shape) == (F, K)
     if not shared and tuple(W.shape[:-2]) != lead:
@@ -154,20 +144,12 @@ def nmf_activations(V, W, n_iter: int = 100, beta: str = "frobenius", H0=None, s
     if H0 is None:
         H0 = initial(lead, F, T, K, seed)[1]
     H0 = _factor(name, b, H0, lead + (K, T), "H0")
-    if b.clips == 0:
-        return _zeros(b, lead + (K, T))
-    H = b.empty(lead + (K, T))
-    if b.device:
-        v, vs, vp = b.placed()
-        with b.device_guard():
-            check(lib.smx_nmf_activations_vram_f32(v, vs, vp, _ptr(W), 0 if shared else F * K, _ptr(H0), K * T, b.clips, F, T, K, n_iter, code,
-                                                   _ptr(H), K * T, b.stream()))
-        return H
-    if shared:                      # the host face takes a dictionary per clip
+    stride = 0 if shared else F * K
+    if shared and not b.device and b.clips:              # the host face takes a dictionary per clip
         W = np.ascontiguousarray(np.broadcast_to(W, lead + (F, K)))
-    fn = lib.smx_nmf_activations_f32 if b.bytes == 4 else lib.smx_nmf_activations_f64
-    check(fn(b.ptr(), _ptr(W), _ptr(H0), b.clips, F, T, K, n_iter, code, _ptr(H)))
-    return b.wrap(H)
+    return b.run((lib.smx_nmf_activations_f32, lib.smx_nmf_activations_f64), (b.ptr(), _ptr(W), _ptr(H0), b.clips, F, T, K, n_iter, code, OUT),
+                 lib.smx_nmf_activations_vram_f32, (*b.placed(), _ptr(W), stride, _ptr(H0), K * T, b.clips, F, T, K, n_iter, code, OUT, K * T, STREAM),
+                 lead + (K, T), skip=b.clips == 0)
 
 
 def _factors(name, W, H):
@@ -192,21 +174,13 @@ def _reconstruct(name, W, H, components, as_mask):
     wide = str(getattr(H, "dtype", "")).endswith("float64")
     check((lib.smx_nmf_reconstruct_f64 if wide else lib.smx_nmf_reconstruct_f32)(None, None, 0, F, T, K, comps, count, as_mask, None))
     b = Batch(H, name)
-    _refuse_device_float64(name, b, "factors are")
+    refuse_device_float64(name, b, "factors are")
     lead = b.shape[:-2]
     W = _factor(name, b, W, lead + (F, K), "W")
     clips = prod(lead)
-    if clips == 0:
-        return _zeros(b, lead + (F, T))
-    out = b.empty(lead + (F, T), overwritten=True)
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_nmf_reconstruct_vram_f32(_ptr(W), F * K, b.ptr(), K * T, clips, F, T, K, comps, count, as_mask, _ptr(out), F * T, T,
-                                                   b.stream()))
-        return out
-    fn = lib.smx_nmf_reconstruct_f32 if b.bytes == 4 else lib.smx_nmf_reconstruct_f64
-    check(fn(_ptr(W), b.ptr(), clips, F, T, K, comps, count, as_mask, _ptr(out)))
-    return b.wrap(out)
+    return b.run((lib.smx_nmf_reconstruct_f32, lib.smx_nmf_reconstruct_f64), (_ptr(W), b.ptr(), clips, F, T, K, comps, count, as_mask, OUT),
+                 lib.smx_nmf_reconstruct_vram_f32, (_ptr(W), F * K, b.ptr(), K * T, clips, F, T, K, comps, count, as_mask, OUT, F * T, T, STREAM),
+                 lead + (F, T), skip=clips == 0, overwritten=True)
 
 
 def nmf_reconstruct(W, H, components=None):
@@ -235,20 +209,12 @@ def nmf_divergence(V, W, H, beta: str = "frobenius"):
     wide = str(getattr(V, "dtype", "")).endswith("float64")
     check((lib.smx_nmf_divergence_f64 if wide else lib.smx_nmf_divergence_f32)(None, None, None, 0, F, T, K, code, None))
     b = _Spectrogram(V, name)
-    _refuse_device_float64(name, b, "spectrograms are")
+    refuse_device_float64(name, b, "spectrograms are")
     lead = b.lead_shape
     W, H = _factor(name, b, W, lead + (F, K), "W"), _factor(name, b, H, lead + (K, T), "H")
-    if b.clips == 0:
-        return _zeros(b, lead + (1,))
-    out = b.empty(lead + (1,))
-    if b.device:
-        v, vs, vp = b.placed()
-        with b.device_guard():
-            check(lib.smx_nmf_divergence_vram_f32(v, vs, vp, _ptr(W), F * K, _ptr(H), K * T, b.clips, F, T, K, code, _ptr(out), b.stream()))
-        return out
-    fn = lib.smx_nmf_divergence_f32 if b.bytes == 4 else lib.smx_nmf_divergence_f64
-    check(fn(b.ptr(), _ptr(W), _ptr(H), b.clips, F, T, K, code, _ptr(out)))
-    return b.wrap(out)
+    return b.run((lib.smx_nmf_divergence_f32, lib.smx_nmf_divergence_f64), (b.ptr(), _ptr(W), _ptr(H), b.clips, F, T, K, code, OUT),
+                 lib.smx_nmf_divergence_vram_f32, (*b.placed(), _ptr(W), F * K, _ptr(H), K * T, b.clips, F, T, K, code, OUT, STREAM),
+                 lead + (1,), skip=b.clips == 0)
 
 
 reconstruct, activations, divergence = nmf_reconstruct, nmf_activations, nmf_divergence

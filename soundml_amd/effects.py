@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from .resample import Config as _ResampleConfig
 from ._lib import check, lib
-from ._tensor import Batch, is_device, is_torch, out_ptr, prod, torch
+from ._tensor import OUT, STREAM, Batch, is_device, is_torch, out_ptr, prod, refuse_device_float64, torch
 
 _PHASE = {"independent": 0, "locked": 1}
 _RESAMPLERS = {}    # (num, den, quality) -> Resample.Config: its filter bank is uploaded once, and freeing one waits for the device
@@ -131,20 +131,12 @@ def phase_vocoder(c, z, rate: float, phase: str = "independent"):
     return torch.from_numpy(out) if was_torch else out
 
 
-def _signal_call(fn, x, out_len, host_fns, dev_fn, args_before, args_after):
+def _signal_call(fn, x, out_len, host, device, args_before, args_after):
     b = Batch(x, fn)
     shape = b.shape
-    lead, n = prod(shape[:-1]), int(shape[-1])
-    y = b.empty(shape[:-1] + (out_len,))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("%s: device-resident float64 audio is not supported; pass a host array" % fn)
-        with b.device_guard():
-            check(dev_fn(*args_before, b.ptr(), lead, n, *args_after, out_ptr(y), b.stream()))
-        return y
-    host_fn = host_fns[0] if b.bytes == 4 else host_fns[1]
-    check(host_fn(*args_before, b.ptr(), lead, n, *args_after, out_ptr(y)))
-    return b.wrap(y)
+    refuse_device_float64(fn, b)
+    args = (*args_before, b.ptr(), prod(shape[:-1]), int(shape[-1]), *args_after, OUT)
+    return b.run(host, args, device, args + (STREAM,), shape[:-1] + (out_len,))
 
 
 def time_stretch(c, x, rate: float, phase: str = "independent"):

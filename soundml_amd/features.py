@@ -3,7 +3,7 @@ from __future__ import annotations
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, prod, refuse_device_float64
 from . import stft as Stft
 
 
@@ -20,18 +20,13 @@ def mel_spectrogram(stft_config, mel_config, x, power: float = 2.0):
     lead_shape = b.shape[:-1]
     lead = prod(lead_shape)
     count = Stft.frames(stft_config, n)
-    out = b.empty(lead_shape + (mel_config.n_mels, count))
-    if b.device:
-        if b.bytes != 4:
-            from . import mel as Mel
-            return Mel.apply(mel_config, Stft.power_spectrum(stft_config, x, power))
-        with b.device_guard():
-            check(lib.smx_mel_spectrogram_f32_dev(stft_config._h, mel_config._h, b.ptr(), lead, n, n,
-                                                  float(power), out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_mel_spectrogram_f32 if b.bytes == 4 else lib.smx_mel_spectrogram_f64
-    check(fn(stft_config._h, mel_config._h, b.ptr(), lead, n, float(power), out_ptr(out)))
-    return b.wrap(out)
+    if b.device and b.bytes != 4:                        # no fused float64 kernel: the composition
+        from . import mel as Mel
+        return Mel.apply(mel_config, Stft.power_spectrum(stft_config, x, power))
+    cfgs = (stft_config._h, mel_config._h)
+    return b.run((lib.smx_mel_spectrogram_f32, lib.smx_mel_spectrogram_f64), (*cfgs, b.ptr(), lead, n, float(power), OUT),
+                 lib.smx_mel_spectrogram_f32_dev, (*cfgs, b.ptr(), lead, n, n, float(power), OUT, STREAM),
+                 lead_shape + (mel_config.n_mels, count))
 
 
 def mfcc(stft_config, mel_config, x, n_mfcc: int = 20, lifter=None):
@@ -49,17 +44,10 @@ def mfcc(stft_config, mel_config, x, n_mfcc: int = 20, lifter=None):
     lead_shape = b.shape[:-1]
     lead = prod(lead_shape)
     count = Stft.frames(stft_config, n)
-    out = b.empty(lead_shape + (int(n_mfcc), count))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("mfcc: device-resident float64 audio is not supported; pass a host array")
-        with b.device_guard():
-            check(lib.smx_mfcc_f32_dev(stft_config._h, mel_config._h, b.ptr(), lead, n, n, int(n_mfcc),
-                                       1 if has_lifter else 0, lift, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_mfcc_f32 if b.bytes == 4 else lib.smx_mfcc_f64
-    check(fn(stft_config._h, mel_config._h, b.ptr(), lead, n, int(n_mfcc), 1 if has_lifter else 0, lift, out_ptr(out)))
-    return b.wrap(out)
+    refuse_device_float64("mfcc", b)
+    cfgs, tail = (stft_config._h, mel_config._h), (int(n_mfcc), 1 if has_lifter else 0, lift, OUT)
+    return b.run((lib.smx_mfcc_f32, lib.smx_mfcc_f64), (*cfgs, b.ptr(), lead, n, *tail),
+                 lib.smx_mfcc_f32_dev, (*cfgs, b.ptr(), lead, n, n, *tail, STREAM), lead_shape + (int(n_mfcc), count))
 
 
 def chroma_stft(stft_config, chroma_config, x, power: float = 2.0, norm="inf"):
@@ -75,17 +63,11 @@ def chroma_stft(stft_config, chroma_config, x, power: float = 2.0, norm="inf"):
     lead_shape = b.shape[:-1]
     lead = prod(lead_shape)
     count = Stft.frames(stft_config, n)
-    out = b.empty(lead_shape + (chroma_config.n_chroma, count))
-    if b.device:
-        if b.bytes != 4:
-            return Chroma.apply(chroma_config, Stft.power_spectrum(stft_config, x, power), norm)
-        with b.device_guard():
-            check(lib.smx_chroma_stft_f32_dev(stft_config._h, chroma_config._h, b.ptr(), lead, n, n, float(power),
-                                              kind, p, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_chroma_stft_f32 if b.bytes == 4 else lib.smx_chroma_stft_f64
-    check(fn(stft_config._h, chroma_config._h, b.ptr(), lead, n, float(power), kind, p, out_ptr(out)))
-    return b.wrap(out)
+    if b.device and b.bytes != 4:                        # no fused float64 kernel: the composition
+        return Chroma.apply(chroma_config, Stft.power_spectrum(stft_config, x, power), norm)
+    cfgs, tail = (stft_config._h, chroma_config._h), (float(power), kind, p, OUT)
+    return b.run((lib.smx_chroma_stft_f32, lib.smx_chroma_stft_f64), (*cfgs, b.ptr(), lead, n, *tail),
+                 lib.smx_chroma_stft_f32_dev, (*cfgs, b.ptr(), lead, n, n, *tail, STREAM), lead_shape + (chroma_config.n_chroma, count))
 
 
 def chroma_cqt(cqt_config, x, n_chroma: int = 12, norm="inf"):
@@ -100,14 +82,9 @@ def chroma_cqt(cqt_config, x, n_chroma: int = 12, norm="inf"):
     n = int(b.shape[-1])
     lead_shape = b.shape[:-1]
     lead = prod(lead_shape)
-    out = b.empty(lead_shape + (n_chroma, Cqt.frames(cqt_config, n)))
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_chroma_cqt_f32_dev(cqt_config._h, b.ptr(), lead, n, max(n, 1), n_chroma, kind, p,
-                                             out_ptr(out) if out.numel() else None, b.stream()))
-        return out
-    check(lib.smx_chroma_cqt_f32(cqt_config._h, b.ptr(), lead, n, n_chroma, kind, p, out_ptr(out) if out.size else None))
-    return b.wrap(out)
+    return b.run(lib.smx_chroma_cqt_f32, (cqt_config._h, b.ptr(), lead, n, n_chroma, kind, p, OUT),
+                 lib.smx_chroma_cqt_f32_dev, (cqt_config._h, b.ptr(), lead, n, max(n, 1), n_chroma, kind, p, OUT, STREAM),
+                 lead_shape + (n_chroma, Cqt.frames(cqt_config, n)), null_empty=True)
 
 
 def _to_db(which, s, reference, amin, top_db):
@@ -116,18 +93,11 @@ def _to_db(which, s, reference, amin, top_db):
         s = np.asarray(s)
     b = Batch(s, which, min_rank=0)
     total = prod(b.shape)
-    out = b.empty(b.shape)
     has_top = top_db is not None
-    args = (total, float(reference), float(amin), 1 if has_top else 0, float(top_db) if has_top else 0.0)
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("%s: device-resident float64 data is not supported; pass a host array" % which)
-        with b.device_guard():
-            check(getattr(lib, "smx_%s_f32_dev" % which)(b.ptr(), *args, out_ptr(out), b.stream()))
-        return out
-    fn = getattr(lib, "smx_%s_%s" % (which, "f32" if b.bytes == 4 else "f64"))
-    check(fn(b.ptr(), *args, out_ptr(out)))
-    return b.wrap(out)
+    args = (b.ptr(), total, float(reference), float(amin), 1 if has_top else 0, float(top_db) if has_top else 0.0, OUT)
+    refuse_device_float64(which, b, "data is")
+    return b.run((getattr(lib, "smx_%s_f32" % which), getattr(lib, "smx_%s_f64" % which)), args,
+                 getattr(lib, "smx_%s_f32_dev" % which), args + (STREAM,), b.shape)
 
 
 def power_to_db(s, reference: float = 1.0, amin: float = 1e-10, top_db=None):

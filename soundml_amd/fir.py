@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, prod
 
 
 def kaiser_beta(attenuation: float) -> float:
@@ -60,10 +60,4 @@ def apply(p: Plan, x):
         raise _lib.InvalidArgument("fir_apply: cannot filter float64 audio (this path is float32)")
     n = int(b.shape[-1])
     lead = prod(b.shape[:-1])
-    out = b.empty(b.shape)
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_fir_apply_f32_dev(p._h, b.ptr(), lead, n, n, out_ptr(out), n, b.stream()))
-        return out
-    check(lib.smx_fir_apply_f32(p._h, b.ptr(), lead, n, out_ptr(out)))
-    return b.wrap(out)
+    return b.run(lib.smx_fir_apply_f32, (p._h, b.ptr(), lead, n, OUT), lib.smx_fir_apply_f32_dev, (p._h, b.ptr(), lead, n, n, OUT, n, STREAM), b.shape)

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, is_device, is_torch, out_ptr, prod, torch
+from ._tensor import OUT, STREAM, Batch, is_device, is_torch, out_ptr, prod, refuse_device_float64, torch
 
 DEFAULT_KERNEL = (31, 31)
 DEFAULT_MARGIN = (1.0, 1.0)
@@ -72,22 +72,14 @@ def _check_real_dtype(fn, x):   # hpss.ml:351-363
             "%s: cannot separate %s spectra (the median kernel carries float32 and float64)" % (fn, name))
 
 
-def _planes(fn, s, params, host_fns, dev_fn):
+def _planes(fn, s, params, host, device):
     _check_rank(fn, len(s.shape))
     _check_real_dtype(fn, s)
     b = Batch(s, fn)
     shape = b.shape
-    lead, bins, frames = prod(shape[:-2]), int(shape[-2]), int(shape[-1])
-    out_h, out_p = b.empty(shape), b.empty(shape)
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("%s: device-resident float64 spectrograms are not supported; pass a host array" % fn)
-        with b.device_guard():
-            check(dev_fn(b.ptr(), lead, bins, frames, *params, out_ptr(out_h), out_ptr(out_p), b.stream()))
-        return out_h, out_p
-    host_fn = host_fns[0] if b.bytes == 4 else host_fns[1]
-    check(host_fn(b.ptr(), lead, bins, frames, *params, out_ptr(out_h), out_ptr(out_p)))
-    return b.wrap(out_h), b.wrap(out_p)
+    refuse_device_float64(fn, b, "spectrograms are")
+    args = (b.ptr(), prod(shape[:-2]), int(shape[-2]), int(shape[-1]), *params, OUT, OUT)
+    return b.run(host, args, device, args + (STREAM,), [shape, shape])
 
 
 def hpss_masks(s, kernel_size=DEFAULT_KERNEL, power: float = 2.0, margin=DEFAULT_MARGIN):
@@ -147,21 +139,10 @@ def _separate(fn, c, x, kernel_size, power, margin, want_h, want_p):
     b = Batch(x, fn)
     shape = b.shape
     lead, n = prod(shape[:-1]), int(shape[-1])
-    y_h = b.empty(shape) if want_h else None
-    y_p = b.empty(shape) if want_p else None
-    ptr = lambda y: out_ptr(y) if y is not None else None
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("%s: device-resident float64 audio is not supported; pass a host array" % fn)
-        for y in (y_h, y_p):
-            if y is not None and y.numel() > 0:
-                y.zero_()
-        with b.device_guard():
-            check(lib.smx_hpss_f32_dev(c._h, b.ptr(), lead, n, *params, ptr(y_h), ptr(y_p), b.stream()))
-        return y_h, y_p
-    host_fn = lib.smx_hpss_f32 if b.bytes == 4 else lib.smx_hpss_f64
-    check(host_fn(c._h, b.ptr(), lead, n, *params, ptr(y_h), ptr(y_p)))
-    return (b.wrap(y_h) if want_h else None), (b.wrap(y_p) if want_p else None)
+    refuse_device_float64(fn, b)
+    args = (c._h, b.ptr(), lead, n, *params, OUT, OUT)
+    return b.run((lib.smx_hpss_f32, lib.smx_hpss_f64), args, lib.smx_hpss_f32_dev, args + (STREAM,),
+                 [shape if want_h else None, shape if want_p else None], prefill=True)
 
 
 def hpss(c, x, kernel_size=DEFAULT_KERNEL, power: float = 2.0, margin=DEFAULT_MARGIN):

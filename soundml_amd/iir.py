@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, is_device, is_torch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, is_device, is_torch, out_ptr, prod, refuse_device_float64, torch
 
 BLOCK = int(lib.smx_iir_block())
 SPAN_BLOCKS = int(lib.smx_iir_span_blocks())
@@ -67,9 +67,7 @@ def zi(c: Config) -> np.ndarray:
     return out
 
 
-def _refuse_device_float64(op, b):
-    if b.device and b.bytes != 4:
-        raise _lib.Failure("%s: device-resident float64 audio is not supported; pass a host array" % op)
+_refuse_device_float64 = refuse_device_float64
 
 
 def _state(c, zi_, lead_shape):
@@ -77,7 +75,6 @@ def _state(c, zi_, lead_shape):
     if zi_ is None:
         return None, False
     if is_device(zi_) and tuple(zi_.shape) == tuple(lead_shape) + (c.sections, 2) and len(lead_shape) > 0:
-        import torch
         return zi_.to(torch.float64).contiguous(), True      # one state per channel, already resident: no copy, no wait
     z = zi_.detach().cpu().numpy() if is_torch(zi_) else np.asarray(zi_)
     z = np.ascontiguousarray(z, dtype=np.float64)
@@ -98,34 +95,31 @@ def apply(c: Config, x, zi=None, return_state: bool = False):
     z, rows = _state(c, zi, lead_shape)
     state_shape = tuple(lead_shape) + (c.sections, 2)
     if lead == 0 or n == 0:                              # nothing to filter: no launch, the state given is the state returned
-        out = b.empty(b.shape)
+        out = b.wrap(b.empty(b.shape))
         if not return_state:
-            return out if b.device else b.wrap(out)
+            return out
         zf = np.zeros(state_shape) if z is None else np.ascontiguousarray(np.broadcast_to(z.cpu().numpy() if is_torch(z) else z, state_shape))
         if b.device:
-            import torch
-            return out, torch.from_numpy(zf).to(b.data.device)
-        return b.wrap(out), b.wrap(zf)
+                return out, torch.from_numpy(zf).to(b.data.device)
+        return out, b.wrap(zf)
     if is_torch(z) and not b.device:
         z = z.cpu().numpy()
     zp = C.c_void_p(z.ctypes.data) if z is not None and not is_torch(z) else None
+    d_rows = zf = None                                   # the float64 states lie on the signal's side
     if b.device:
-        import torch
-        out = b.empty(b.shape)
-        with b.device_guard():
-            zf = torch.empty(state_shape, dtype=torch.float64, device=b.data.device) if return_state else None
-            d_rows = (z if is_torch(z) else torch.from_numpy(z).to(b.data.device)) if rows else None
-            check(lib.smx_iir_apply_card_f32(c._h, b.stream(), b.ptr(), lead, n, n, None if rows else zp,
-                                             C.c_void_p(d_rows.data_ptr()) if rows else None, out_ptr(out),
-                                             C.c_void_p(zf.data_ptr()) if return_state else None))
-            if rows:
-                d_rows.record_stream(torch.cuda.current_stream(b.data.device))
-        return (out, zf) if return_state else out
-    out = b.empty(b.shape, overwritten=True)
-    zf = np.zeros(state_shape) if return_state else None
-    fn = lib.smx_iir_apply_f32 if b.bytes == 4 else lib.smx_iir_apply_f64
-    check(fn(c._h, b.ptr(), lead, n, zp, 1 if rows else 0, out_ptr(out), C.c_void_p(zf.ctypes.data) if return_state else None))
-    return (b.wrap(out), b.wrap(zf)) if return_state else b.wrap(out)
+        if return_state:
+            zf = torch.empty(state_shape, dtype=torch.float64, device=b.data.device)
+        if rows:
+            d_rows = z if is_torch(z) else torch.from_numpy(z).to(b.data.device)
+    elif return_state:
+        zf = np.zeros(state_shape)
+    ptr = lambda t: None if t is None else out_ptr(t)
+    out = b.run((lib.smx_iir_apply_f32, lib.smx_iir_apply_f64), (c._h, b.ptr(), lead, n, zp, 1 if rows else 0, OUT, ptr(zf)),
+                lib.smx_iir_apply_card_f32, (c._h, STREAM, b.ptr(), lead, n, n, None if rows else zp, ptr(d_rows), OUT, ptr(zf)),
+                b.shape, overwritten=True)
+    if d_rows is not None:
+        d_rows.record_stream(torch.cuda.current_stream(b.data.device))
+    return (out, b.wrap(zf)) if return_state else out
 
 
 def filtfilt(c: Config, x):
@@ -135,18 +129,9 @@ def filtfilt(c: Config, x):
     n, lead_shape = int(b.shape[-1]), b.shape[:-1]
     lead = prod(lead_shape)
     check(lib.smx_iir_filtfilt_f32(c._h, None, 0, n, None))          # the section at a pole, then the length, worded by the ABI
-    if lead == 0:
-        out = b.empty(b.shape)
-        return out if b.device else b.wrap(out)
-    if b.device:
-        out = b.empty(b.shape)
-        with b.device_guard():
-            check(lib.smx_iir_filtfilt_card_f32(c._h, b.stream(), b.ptr(), lead, n, n, out_ptr(out)))
-        return out
-    out = b.empty(b.shape, overwritten=True)
-    fn = lib.smx_iir_filtfilt_f32 if b.bytes == 4 else lib.smx_iir_filtfilt_f64
-    check(fn(c._h, b.ptr(), lead, n, out_ptr(out)))
-    return b.wrap(out)
+    return b.run((lib.smx_iir_filtfilt_f32, lib.smx_iir_filtfilt_f64), (c._h, b.ptr(), lead, n, OUT),
+                 lib.smx_iir_filtfilt_card_f32, (c._h, STREAM, b.ptr(), lead, n, n, OUT), b.shape,
+                 skip=lead == 0, empty="uninitialised", overwritten=True)
 
 
 class Kernel:
@@ -186,7 +171,6 @@ class Kernel:
         shape = tuple(chunk.shape)
         if len(shape) < 1:
             raise _lib.InvalidArgument("step: cannot analyse a rank-zero tensor (the time axis must exist)")
-        device = is_device(chunk)
         m = int(shape[-1])
         if m == 0:
             check(lib.smx_iir_kernel_step_f32(self._h, None, 0, None))     # a drained kernel refuses an empty chunk too
@@ -196,15 +180,8 @@ class Kernel:
                                        % (shape[:-1], self.lead_shape))
         b = Batch(chunk, "step")
         _refuse_device_float64("step", b)
-        if device:
-            out = b.empty(b.shape)
-            with b.device_guard():
-                check(lib.smx_iir_kernel_step_card_f32(self._h, b.stream(), b.ptr(), m, m, out_ptr(out)))
-            return out
-        out = b.empty(b.shape, overwritten=True)
-        fn = lib.smx_iir_kernel_step_f32 if b.bytes == 4 else lib.smx_iir_kernel_step_f64
-        check(fn(self._h, b.ptr(), m, out_ptr(out)))
-        return b.wrap(out)
+        return b.run((lib.smx_iir_kernel_step_f32, lib.smx_iir_kernel_step_f64), (self._h, b.ptr(), m, OUT),
+                     lib.smx_iir_kernel_step_card_f32, (self._h, STREAM, b.ptr(), m, m, OUT), b.shape, overwritten=True)
 
     __call__ = step
 

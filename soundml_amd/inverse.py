@@ -12,7 +12,7 @@ from __future__ import annotations
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, prod
 from . import mel as Mel
 from . import stft as Stft
 
@@ -52,15 +52,11 @@ def mfcc_to_mel(c, n_mels: int, lifter=None, reference: float = 1.0):
     lead = prod(lead_shape)
     has_lifter = lifter is not None
     tail = (int(n_mels), 1 if has_lifter else 0, float(lifter) if has_lifter else 0.0, float(reference))
-    sfx = "f32" if b.bytes == 4 else "f64"
-    check(getattr(lib, "smx_mfcc_to_mel_%s" % sfx)(None, 0, n_mfcc, 0, *tail, None))   # the checks first
-    out = b.empty(lead_shape + (int(n_mels), frames))
-    if b.device:
-        with b.device_guard():
-            check(getattr(lib, "smx_mfcc_to_mel_%s_dev" % sfx)(b.ptr(), lead, n_mfcc, frames, *tail, out_ptr(out), b.stream()))
-        return out
-    check(getattr(lib, "smx_mfcc_to_mel_%s" % sfx)(b.ptr(), lead, n_mfcc, frames, *tail, out_ptr(out)))
-    return b.wrap(out)
+    host = (lib.smx_mfcc_to_mel_f32, lib.smx_mfcc_to_mel_f64)
+    check(b.pick(host)(None, 0, n_mfcc, 0, *tail, None))   # the checks first
+    args = (b.ptr(), lead, n_mfcc, frames, *tail, OUT)
+    return b.run(host, args, (lib.smx_mfcc_to_mel_f32_dev, lib.smx_mfcc_to_mel_f64_dev), args + (STREAM,),
+                 lead_shape + (int(n_mels), frames))
 
 
 def mfcc_to_audio(stft_config, mel_config, c, lifter=None, reference: float = 1.0, power: float = 2.0, n_iter: int = 200,

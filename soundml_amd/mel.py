@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, Stateless, prod
 
 
 class Config:
@@ -81,16 +81,9 @@ def apply(c: Config, s):
     lead_shape = b.shape[:-2]
     bins, frames = int(b.shape[-2]), int(b.shape[-1])
     lead = prod(lead_shape)
-    out = b.empty(lead_shape + (c.n_mels, frames))
-    sfx = "f32" if b.bytes == 4 else "f64"
-    if b.device:
-        with b.device_guard():
-            fn = getattr(lib, "smx_mel_apply_%s_dev" % sfx)
-            check(fn(c._h, b.ptr(), lead, bins, frames, out_ptr(out), b.stream()))
-        return out
-    fn = getattr(lib, "smx_mel_apply_%s" % sfx)
-    check(fn(c._h, b.ptr(), lead, bins, frames, out_ptr(out)))
-    return b.wrap(out)
+    args = (c._h, b.ptr(), lead, bins, frames, OUT)
+    return b.run((lib.smx_mel_apply_f32, lib.smx_mel_apply_f64), args, (lib.smx_mel_apply_f32_dev, lib.smx_mel_apply_f64_dev),
+                 args + (STREAM,), lead_shape + (c.n_mels, frames))
 
 
 def _invert(c: Config, m, n_iter, power):
@@ -102,16 +95,10 @@ def _invert(c: Config, m, n_iter, power):
     lead_shape = b.shape[:-2]
     n_mels, frames = int(b.shape[-2]), int(b.shape[-1])
     lead = prod(lead_shape)
-    sfx = "f32" if b.bytes == 4 else "f64"
-    args = (lead, n_mels, frames, int(n_iter), float(power))
-    check(getattr(lib, "smx_mel_invert_%s" % sfx)(c._h, None, 0, n_mels, 0, int(n_iter), float(power), None))   # the checks first
-    out = b.empty(lead_shape + (c.bins, frames))
-    if b.device:
-        with b.device_guard():
-            check(getattr(lib, "smx_mel_invert_%s_dev" % sfx)(c._h, b.ptr(), *args, out_ptr(out), b.stream()))
-        return out
-    check(getattr(lib, "smx_mel_invert_%s" % sfx)(c._h, b.ptr(), *args, out_ptr(out)))
-    return b.wrap(out)
+    host = (lib.smx_mel_invert_f32, lib.smx_mel_invert_f64)
+    args = (c._h, b.ptr(), lead, n_mels, frames, int(n_iter), float(power), OUT)
+    check(b.pick(host)(c._h, None, 0, n_mels, 0, int(n_iter), float(power), None))   # the checks first
+    return b.run(host, args, (lib.smx_mel_invert_f32_dev, lib.smx_mel_invert_f64_dev), args + (STREAM,), lead_shape + (c.bins, frames))
 
 
 def invert(c: Config, m, n_iter: int = 200):
@@ -123,5 +110,4 @@ def invert(c: Config, m, n_iter: int = 200):
 
 def stage(c: Config):
     """``Mel.stage c`` (mel.ml:233): ``apply c`` as a memoryless Pipeline stage."""
-    from ._tensor import Stateless
     return Stateless(lambda s: apply(c, s))

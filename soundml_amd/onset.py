@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, is_torch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, copy, is_torch, join, prod, refuse_device_float64
 from . import stft as Stft
 
 
@@ -27,16 +27,10 @@ def onset_strength(stft_config, mel_config, x, lag: int = 1):
     n = int(b.shape[-1])
     lead_shape = b.shape[:-1]
     lead = prod(lead_shape)
-    out = b.empty(lead_shape + (Stft.frames(stft_config, n),))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("onset_strength: device-resident float64 audio is not supported; pass a host array")
-        with b.device_guard():
-            check(lib.smx_onset_strength_dev_f32(stft_config._h, mel_config._h, b.ptr(), lead, n, n, lag, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_onset_strength_f32 if b.bytes == 4 else lib.smx_onset_strength_f64
-    check(fn(stft_config._h, mel_config._h, b.ptr(), lead, n, lag, out_ptr(out)))
-    return b.wrap(out)
+    shape = lead_shape + (Stft.frames(stft_config, n),)
+    refuse_device_float64("onset_strength", b)
+    return b.run((lib.smx_onset_strength_f32, lib.smx_onset_strength_f64), (stft_config._h, mel_config._h, b.ptr(), lead, n, lag, OUT),
+                 lib.smx_onset_strength_dev_f32, (stft_config._h, mel_config._h, b.ptr(), lead, n, n, lag, OUT, STREAM), shape)
 
 
 def flux(s, lag: int = 1):
@@ -50,19 +44,14 @@ def flux(s, lag: int = 1):
     b = Batch(s, op)
     lead_shape, bins, frames = b.shape[:-2], int(b.shape[-2]), int(b.shape[-1])
     lead = prod(lead_shape)
-    out = b.empty(lead_shape + (frames,))
-    if lead == 0 or bins == 0 or frames == 0:
+    skip = lead == 0 or bins == 0 or frames == 0
+    if skip:
         check(lib.smx_onset_flux_f32(None, lead, bins, frames, int(lag), None))
-        return b.wrap(out)
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("%s: device-resident float64 spectrograms are not supported; pass a host array" % op)
-        with b.device_guard():
-            check(lib.smx_onset_flux_dev_f32(b.ptr(), lead, bins, frames, int(lag), out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_onset_flux_f32 if b.bytes == 4 else lib.smx_onset_flux_f64
-    check(fn(b.ptr(), lead, bins, frames, int(lag), out_ptr(out)))
-    return b.wrap(out)
+    else:
+        refuse_device_float64(op, b, "spectrograms are")
+    return b.run((lib.smx_onset_flux_f32, lib.smx_onset_flux_f64), (b.ptr(), lead, bins, frames, int(lag), OUT),
+                 lib.smx_onset_flux_dev_f32, (b.ptr(), lead, bins, frames, int(lag), OUT, STREAM), lead_shape + (frames,),
+                 skip=skip, empty="uninitialised")
 
 
 class OnsetStrengthStage:
@@ -83,14 +72,13 @@ class OnsetStrengthStage:
         else:
             keep = int(self._carry.shape[-1])
             if is_torch(chunk):
-                import torch
-                ext = torch.cat([self._carry.to(device=chunk.device, dtype=chunk.dtype), chunk], dim=-1)
+                ext = join([self._carry.to(device=chunk.device, dtype=chunk.dtype), chunk])
             else:
-                ext = np.concatenate([self._carry, np.asarray(chunk)], axis=-1)
+                ext = join([self._carry, np.asarray(chunk)])
         out = flux(ext, self.lag)[..., keep:]
         held = min(self.lag, int(ext.shape[-1]))
         tail = ext[..., int(ext.shape[-1]) - held:]
-        self._carry = tail.clone() if is_torch(tail) else np.array(tail)
+        self._carry = copy(tail)
         return out.contiguous() if is_torch(out) else np.ascontiguousarray(out)
 
     __call__ = step

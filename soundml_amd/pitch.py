@@ -18,11 +18,14 @@ definition).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 
+import numpy as np
+
 from ._lib import InvalidArgument, check, lib
-from ._tensor import Batch, out_ptr, prod
-from .energy import EnergyStage, RMS, _refuse_device_float64, _zeros, frames       # noqa: F401  (frames: the grid is rms')
+from ._tensor import OUT, STREAM, Batch, FramedStage, prod, refuse_device_float64
+from .energy import frames       # noqa: F401  (the grid is rms')
 
 
 def _hop(frame_length, hop):
@@ -38,26 +41,24 @@ def lag_range(sample_rate: int, fmin: float, fmax: float, frame_length: int = 20
     return int(math.floor(sr / fmax)), cap if longest >= cap else int(math.ceil(longest))
 
 
+def _batch(name, x, fl, hop):
+    b = Batch(x, name)
+    refuse_device_float64(name, b)
+    n = int(b.shape[-1])
+    return b, n, b.shape[:-1], prod(b.shape[:-1]), frames(n, fl, hop)
+
+
 def _run(name, x, params, count_of, host, resident, want_ap):
     """one frame call: the parameters are checked before the tensor is looked at"""
     b = Batch(x, name)
-    _refuse_device_float64(name, b)
+    refuse_device_float64(name, b)
     n = int(b.shape[-1])
-    lead_shape = b.shape[:-1]
-    lead = prod(lead_shape)
+    lead = prod(b.shape[:-1])
     count = count_of(n)
-    shape = lead_shape + (1, count)
-    if lead == 0 or count == 0:
-        f0 = _zeros(b, shape)
-        return (f0, _zeros(b, shape)) if want_ap else f0
-    f0 = b.empty(shape)
-    ap = b.empty(shape) if want_ap else None
-    if b.device:
-        with b.device_guard():
-            check(resident(b.ptr(), lead, n, n, *params, out_ptr(f0), out_ptr(ap) if want_ap else None, b.stream()))
-        return (f0, ap) if want_ap else f0
-    check(host[b.bytes](b.ptr(), lead, n, *params, out_ptr(f0), out_ptr(ap) if want_ap else None))
-    return (b.wrap(f0), b.wrap(ap)) if want_ap else b.wrap(f0)
+    shape = b.shape[:-1] + (1, count)
+    f0, ap = b.run(host, (b.ptr(), lead, n, *params, OUT, OUT), resident, (b.ptr(), lead, n, n, *params, OUT, OUT, STREAM),
+                   [shape, shape if want_ap else None], skip=lead == 0 or count == 0)
+    return (f0, ap) if want_ap else f0
 
 
 def yin(x, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: int = 2048, hop=None, trough_threshold: float = 0.1,
@@ -70,7 +71,7 @@ def yin(x, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: int
     fl, hop = int(frame_length), _hop(frame_length, hop)
     params = (int(sample_rate), float(fmin), float(fmax), fl, hop, float(trough_threshold))
     check(lib.smx_yin_f32(None, 0, 0, *params, None, None))
-    return _run("yin", x, params, lambda n: frames(n, fl, hop), {4: lib.smx_yin_f32, 8: lib.smx_yin_f64}, lib.smx_yin_resident_f32,
+    return _run("yin", x, params, lambda n: frames(n, fl, hop), (lib.smx_yin_f32, lib.smx_yin_f64), lib.smx_yin_resident_f32,
                 bool(return_aperiodicity))
 
 
@@ -82,22 +83,10 @@ def yin_difference(x, fmin: float, fmax: float, sample_rate: int = 22050, frame_
     params = (int(sample_rate), float(fmin), float(fmax), fl, hop)
     check(lib.smx_yin_difference_f32(None, 0, 0, *params, None))
     lags = lag_range(sample_rate, fmin, fmax, fl)[1] + 1
-    b = Batch(x, name)
-    _refuse_device_float64(name, b)
-    n = int(b.shape[-1])
-    lead_shape = b.shape[:-1]
-    lead = prod(lead_shape)
-    count = frames(n, fl, hop)
-    if lead == 0 or count == 0:
-        return _zeros(b, lead_shape + (lags, count))
-    out = b.empty(lead_shape + (lags, count))
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_yin_difference_resident_f32(b.ptr(), lead, n, n, *params, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_yin_difference_f32 if b.bytes == 4 else lib.smx_yin_difference_f64
-    check(fn(b.ptr(), lead, n, *params, out_ptr(out)))
-    return b.wrap(out)
+    b, n, lead_shape, lead, count = _batch(name, x, fl, hop)
+    return b.run((lib.smx_yin_difference_f32, lib.smx_yin_difference_f64), (b.ptr(), lead, n, *params, OUT),
+                 lib.smx_yin_difference_resident_f32, (b.ptr(), lead, n, n, *params, OUT, STREAM), lead_shape + (lags, count),
+                 skip=lead == 0 or count == 0)
 
 
 def segment_frames(samples, count: int, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: int = 2048, hop=None,
@@ -107,28 +96,23 @@ def segment_frames(samples, count: int, fmin: float, fmax: float, sample_rate: i
     fl, hop, count = int(frame_length), _hop(frame_length, hop), int(count)
     params = (count, int(sample_rate), float(fmin), float(fmax), fl, hop, float(trough_threshold))
     check(lib.smx_yin_frames_f32(None, 0, 0, 0, *params[1:], None, None))
-    return _run("yin_stage", samples, params, lambda n: count, {4: lib.smx_yin_frames_f32, 8: lib.smx_yin_frames_f64},
+    return _run("yin_stage", samples, params, lambda n: count, (lib.smx_yin_frames_f32, lib.smx_yin_frames_f64),
                 lib.smx_yin_frames_resident_f32, bool(return_aperiodicity))
 
 
-class YinStage(EnergyStage):
-    """The streaming form of ``yin``: the carry of the energy stages (the pending suffix of the padded stream, the skip when the
-    hop outruns the data, zero borders as rms') over this module's segment call.  Only shapes decide the control flow: device
+class YinStage(FramedStage):
+    """The streaming form of ``yin``: the framed-stream carry (the pending suffix of the padded stream, the skip when the hop
+    outruns the data) with zero borders, as rms', over this module's segment call.  Only shapes decide the control flow: device
     chunks cause no synchronisation.  A step returns [...; 1; k], a pair with ``return_aperiodicity``, or None."""
 
     def __init__(self, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: int = 2048, hop=None,
                  trough_threshold: float = 0.1, return_aperiodicity: bool = False):
-        self.op = RMS                                    # the borders are zeros
-        self.name = "yin_stage"
-        self.frame_length, self.hop, self.threshold = int(frame_length), _hop(frame_length, hop), float(trough_threshold)
+        self.threshold = float(trough_threshold)
         self.fmin, self.fmax, self.sample_rate = float(fmin), float(fmax), int(sample_rate)
         self.return_aperiodicity = bool(return_aperiodicity)
-        check(lib.smx_yin_frames_f32(None, 0, 0, 0, self.sample_rate, self.fmin, self.fmax, self.frame_length, self.hop, self.threshold,
-                                     None, None))
-        self.border = self.frame_length // 2
-        self.latency = self.border
-        self.rate = (1, self.hop)
-        self.reset()
+        check(lib.smx_yin_frames_f32(None, 0, 0, 0, self.sample_rate, self.fmin, self.fmax, int(frame_length), _hop(frame_length, hop),
+                                     self.threshold, None, None))
+        super().__init__("yin_stage", frame_length, _hop(frame_length, hop), "zeros")
 
     def _segment(self, samples, count):
         return segment_frames(samples, count, self.fmin, self.fmax, self.sample_rate, self.frame_length, self.hop, self.threshold,
@@ -155,7 +139,6 @@ def _pyin_params(fmin, fmax, sample_rate, frame_length, hop, n_thresholds, beta_
 
 def pyin_bins(fmin: float, fmax: float, resolution: float = 0.1) -> int:
     """The pitch bins between ``fmin`` and ``fmax``: ``floor(12 bps log2(fmax / fmin)) + 1`` with ``bps = ceil(1 / resolution)``."""
-    import ctypes as C
     n = C.c_int64()
     check(lib.smx_pyin_bins(float(fmin), float(fmax), float(resolution), C.byref(n)))
     return int(n.value)
@@ -164,7 +147,6 @@ def pyin_bins(fmin: float, fmax: float, resolution: float = 0.1) -> int:
 def pyin_half_width(sample_rate: int = 22050, hop: int = 512, resolution: float = 0.1, max_transition_rate: float = 35.92) -> int:
     """h, the half-width of the transition band in bins: ``(m bps) // 2`` with ``m`` the semitones a pitch may move per frame,
     ``max_transition_rate * 12 * hop / sample_rate`` rounded half to even."""
-    import ctypes as C
     h = C.c_int64()
     check(lib.smx_pyin_half_width(int(sample_rate), int(hop), float(resolution), float(max_transition_rate), C.byref(h)))
     return int(h.value)
@@ -176,7 +158,6 @@ def pyin_tables(fmin: float, fmax: float, sample_rate: int = 22050, frame_length
     """The host tables of the definition as float64 numpy arrays: ``thr`` [n + 1], ``beta`` [n], ``E`` [maxr], ``Z`` [maxr + 1]
     (``Z[0]`` = 0), ``freq`` [n_bins], ``edge`` [n_bins - 1] (b = 1 ..), ``tri`` [2 h + 1], ``rs`` [n_bins]; also ``n_bins``, ``h`` and
     ``maxr``, the most troughs a frame can have."""
-    import numpy as np
     params = _pyin_params(fmin, fmax, sample_rate, frame_length, hop, n_thresholds, beta_parameters, boltzmann_parameter, resolution,
                           max_transition_rate, switch_prob, no_trough_prob)
     check(lib.smx_pyin_tables(*params, *([None] * 8)))
@@ -190,11 +171,6 @@ def pyin_tables(fmin: float, fmax: float, sample_rate: int = 22050, frame_length
     return out
 
 
-def _pyin_batch(name, x, fl, hop):
-    b = Batch(x, name)
-    _refuse_device_float64(name, b)
-    n = int(b.shape[-1])
-    return b, n, b.shape[:-1], prod(b.shape[:-1]), frames(n, fl, hop)
 
 
 def pyin(x, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: int = 2048, hop=None, n_thresholds: int = 100,
@@ -211,18 +187,10 @@ def pyin(x, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: in
                           max_transition_rate, switch_prob, no_trough_prob)
     fill = (1, 0.0) if fill_na is None else (0, float(fill_na))
     check(lib.smx_pyin_f32(None, 0, 0, *params, *fill, None, None, None))
-    b, n, lead_shape, lead, count = _pyin_batch(name, x, params[3], params[4])
-    shape = lead_shape + (1, count)
-    if lead == 0 or count == 0:
-        return _zeros(b, shape), _zeros(b, shape), _zeros(b, shape)
-    outs = [b.empty(shape) for _ in range(3)]
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_pyin_accel_f32(b.ptr(), lead, n, n, *params, *fill, *(out_ptr(o) for o in outs), b.stream()))
-        return tuple(outs)
-    fn = lib.smx_pyin_f32 if b.bytes == 4 else lib.smx_pyin_f64
-    check(fn(b.ptr(), lead, n, *params, *fill, *(out_ptr(o) for o in outs)))
-    return tuple(b.wrap(o) for o in outs)
+    b, n, lead_shape, lead, count = _batch(name, x, params[3], params[4])
+    return b.run((lib.smx_pyin_f32, lib.smx_pyin_f64), (b.ptr(), lead, n, *params, *fill, OUT, OUT, OUT),
+                 lib.smx_pyin_accel_f32, (b.ptr(), lead, n, n, *params, *fill, OUT, OUT, OUT, STREAM), [lead_shape + (1, count)] * 3,
+                 skip=lead == 0 or count == 0)
 
 
 def pyin_observation(x, fmin: float, fmax: float, sample_rate: int = 22050, frame_length: int = 2048, hop=None, n_thresholds: int = 100,
@@ -235,18 +203,10 @@ def pyin_observation(x, fmin: float, fmax: float, sample_rate: int = 22050, fram
                           max_transition_rate, switch_prob, no_trough_prob)
     check(lib.smx_pyin_observation_f32(None, 0, 0, *params, None))
     states = 2 * pyin_bins(fmin, fmax, resolution)
-    b, n, lead_shape, lead, count = _pyin_batch(name, x, params[3], params[4])
-    shape = lead_shape + (states, count)
-    if lead == 0 or count == 0:
-        return _zeros(b, shape)
-    out = b.empty(shape)
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_pyin_observation_accel_f32(b.ptr(), lead, n, n, *params, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_pyin_observation_f32 if b.bytes == 4 else lib.smx_pyin_observation_f64
-    check(fn(b.ptr(), lead, n, *params, out_ptr(out)))
-    return b.wrap(out)
+    b, n, lead_shape, lead, count = _batch(name, x, params[3], params[4])
+    return b.run((lib.smx_pyin_observation_f32, lib.smx_pyin_observation_f64), (b.ptr(), lead, n, *params, OUT),
+                 lib.smx_pyin_observation_accel_f32, (b.ptr(), lead, n, n, *params, OUT, STREAM), lead_shape + (states, count),
+                 skip=lead == 0 or count == 0)
 
 
 def pyin_decode(obs, half_width: int, switch_prob: float = 0.01):
@@ -257,21 +217,15 @@ def pyin_decode(obs, half_width: int, switch_prob: float = 0.01):
     h, sp = int(half_width), float(switch_prob)
     check(lib.smx_pyin_decode_f32(None, 0, 0, 0, h, sp, None))
     b = Batch(obs, name)
-    _refuse_device_float64(name, b, "observations are")
+    refuse_device_float64(name, b, "observations are")
     if len(b.shape) < 2:
         raise InvalidArgument("%s: cannot decode a tensor of rank %d (the state and frame axes must exist)" % (name, len(b.shape)))
     states, count = int(b.shape[-2]), int(b.shape[-1])
     lead_shape = b.shape[:-2]
     lead = prod(lead_shape)
-    check(lib.smx_pyin_decode_f32(None, lead, states, count, h, sp, None) if lead == 0 or count == 0 else 0)
-    shape = lead_shape + (1, count)
-    if lead == 0 or count == 0:
-        return _zeros(b, shape)
-    out = b.empty(shape)
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_pyin_decode_accel_f32(b.ptr(), lead, states, count, states * count, h, sp, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_pyin_decode_f32 if b.bytes == 4 else lib.smx_pyin_decode_f64
-    check(fn(b.ptr(), lead, states, count, h, sp, out_ptr(out)))
-    return b.wrap(out)
+    skip = lead == 0 or count == 0
+    if skip:
+        check(lib.smx_pyin_decode_f32(None, lead, states, count, h, sp, None))
+    return b.run((lib.smx_pyin_decode_f32, lib.smx_pyin_decode_f64), (b.ptr(), lead, states, count, h, sp, OUT),
+                 lib.smx_pyin_decode_accel_f32, (b.ptr(), lead, states, count, states * count, h, sp, OUT, STREAM), lead_shape + (1, count),
+                 skip=skip)

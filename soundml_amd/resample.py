@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, out_ptr, prod
 
 
 def ols_geom(rate: int, l: int, m: int, k: int):
@@ -89,13 +89,8 @@ class Stage:
         n = int(b.shape[-1])
         lead = prod(b.shape[:-1])
         n_out = st.out_length(n)
-        out = b.empty(tuple(b.shape[:-1]) + (n_out,))
-        if b.device:
-            with b.device_guard():
-                check(lib.smx_resample_stage_apply_f32_dev(st._h, b.ptr(), lead, n, n, out_ptr(out), n_out, b.stream()))
-            return out
-        check(lib.smx_resample_stage_apply_f32(st._h, b.ptr(), lead, n, out_ptr(out)))
-        return b.wrap(out)
+        return b.run(lib.smx_resample_stage_apply_f32, (st._h, b.ptr(), lead, n, OUT),
+                     lib.smx_resample_stage_apply_f32_dev, (st._h, b.ptr(), lead, n, n, OUT, n_out, STREAM), tuple(b.shape[:-1]) + (n_out,))
 
 
 class Kernel:

@@ -10,7 +10,7 @@ such module; the parameters carry the usual names.
 
 Float64 inside, one rounding to the dtype of the input.  Every sum has one order, a function of the clip's own values
 (include/soundml_amd.h words the definitions), so a leading slice of a batch gives the batch's slice bit for bit.
-Device tensors run on the caller's stream and nothing synchronises; device-resident float64 is refused.
+Device tensors run on the caller's stream and nothing synchronises; float64 on the device is refused.
 """
 from __future__ import annotations
 
@@ -20,8 +20,7 @@ import numpy as np
 
 from . import _lib, window as Window
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
-from .energy import _refuse_device_float64, _zeros
+from ._tensor import OUT, STREAM, Batch, prod, refuse_device_float64
 
 
 def _window(name, kind):
@@ -34,7 +33,7 @@ def _window(name, kind):
 
 def _batch(name, env):
     b = Batch(env, name)
-    _refuse_device_float64(name, b, "envelopes are")
+    refuse_device_float64(name, b, "envelopes are")
     return b, int(b.shape[-1]), b.shape[:-1], prod(b.shape[:-1])
 
 
@@ -50,34 +49,17 @@ def tempogram(env, win_length: int = 384, window="hann", norm: bool = True):
     params = (W, kind, param, 1 if norm else 0)
     check(lib.smx_rhythm_tempogram_f32(None, 0, 0, *params, None))
     b, frames, lead_shape, lead = _batch(name, env)
-    shape = lead_shape + (W, frames)
-    if lead == 0 or frames == 0:
-        return _zeros(b, shape)
-    out = b.empty(shape, overwritten=True)
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_rhythm_tempogram_gpu_f32(b.ptr(), lead, frames, frames, *params, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_rhythm_tempogram_f32 if b.bytes == 4 else lib.smx_rhythm_tempogram_f64
-    check(fn(b.ptr(), lead, frames, *params, out_ptr(out)))
-    return b.wrap(out)
+    return b.run((lib.smx_rhythm_tempogram_f32, lib.smx_rhythm_tempogram_f64), (b.ptr(), lead, frames, *params, OUT),
+                 lib.smx_rhythm_tempogram_gpu_f32, (b.ptr(), lead, frames, frames, *params, OUT, STREAM), lead_shape + (W, frames),
+                 skip=lead == 0 or frames == 0, overwritten=True)
 
 
 def _tempo(name, env, sample_rate, hop, win_length, start_bpm, std_bpm, max_tempo, want_lag):
     params = (int(sample_rate), int(hop), int(win_length), float(start_bpm), float(std_bpm), float(max_tempo), want_lag)
     check(lib.smx_rhythm_tempo_f32(None, 0, 0, *params, None))
     b, frames, lead_shape, lead = _batch(name, env)
-    shape = lead_shape + (1,)
-    if lead == 0:
-        return _zeros(b, shape)
-    out = b.empty(shape)
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_rhythm_tempo_gpu_f32(b.ptr(), lead, frames, frames, *params, out_ptr(out), b.stream()))
-        return out
-    fn = lib.smx_rhythm_tempo_f32 if b.bytes == 4 else lib.smx_rhythm_tempo_f64
-    check(fn(b.ptr(), lead, frames, *params, out_ptr(out)))
-    return b.wrap(out)
+    return b.run((lib.smx_rhythm_tempo_f32, lib.smx_rhythm_tempo_f64), (b.ptr(), lead, frames, *params, OUT),
+                 lib.smx_rhythm_tempo_gpu_f32, (b.ptr(), lead, frames, frames, *params, OUT, STREAM), lead_shape + (1,), skip=lead == 0)
 
 
 def tempo(env, sample_rate: int = 22050, hop: int = 512, win_length: int = 384, start_bpm: float = 120.0, std_bpm: float = 1.0,
@@ -141,16 +123,9 @@ def beat_track(env, sample_rate: int = 22050, hop: int = 512, bpm=None, win_leng
               1 if trim else 0)
     check(lib.smx_rhythm_beat_track_f32(None, 0, 0, *params, None, None))
     b, frames, lead_shape, lead = _batch(name, env)
-    if lead == 0:
-        return _zeros(b, lead_shape + (1,)), _zeros(b, lead_shape + (frames,))
-    bpm_out, beats = b.empty(lead_shape + (1,)), b.empty(lead_shape + (frames,))
-    if b.device:
-        with b.device_guard():
-            check(lib.smx_rhythm_beat_track_gpu_f32(b.ptr(), lead, frames, frames, *params, out_ptr(bpm_out), out_ptr(beats), b.stream()))
-        return bpm_out, beats
-    fn = lib.smx_rhythm_beat_track_f32 if b.bytes == 4 else lib.smx_rhythm_beat_track_f64
-    check(fn(b.ptr(), lead, frames, *params, out_ptr(bpm_out), out_ptr(beats)))
-    return b.wrap(bpm_out), b.wrap(beats)
+    return b.run((lib.smx_rhythm_beat_track_f32, lib.smx_rhythm_beat_track_f64), (b.ptr(), lead, frames, *params, OUT, OUT),
+                 lib.smx_rhythm_beat_track_gpu_f32, (b.ptr(), lead, frames, frames, *params, OUT, OUT, STREAM),
+                 [lead_shape + (1,), lead_shape + (frames,)], skip=lead == 0)
 
 
 def beat_frames(beats):

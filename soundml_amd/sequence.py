@@ -22,8 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
-from .energy import _refuse_device_float64, _zeros
+from ._tensor import OUT, STREAM, Batch, prod, refuse_device_float64
 
 
 def _tile():
@@ -68,7 +67,7 @@ def _pairs(name, X, Y, check_call):
     bx, by = Batch(X, name), Batch(Y, name)
     if bx.device != by.device or bx.bytes != by.bytes:
         raise _lib.InvalidArgument("%s: X and Y must share the dtype and lie on the same side (host or device)" % name)
-    _refuse_device_float64(name, bx, "features are")
+    refuse_device_float64(name, bx, "features are")
     return bx, by, sx[:-2], prod(sx[:-2]), d, n, m
 
 
@@ -78,17 +77,9 @@ def cost_matrix(X, Y, metric: str = "euclidean"):
     name = "cost_matrix"
     k = _metric(name, metric)
     bx, by, lead_shape, pairs, d, n, m = _pairs(name, X, Y, lambda d, n, m: check(lib.smx_cost_matrix_f32(None, None, 0, d, n, m, k, None)))
-    shape = lead_shape + (n, m)
-    if pairs == 0:
-        return _zeros(bx, shape)
-    out = bx.empty(shape, overwritten=True)
-    if bx.device:
-        with bx.device_guard():
-            check(lib.smx_cost_matrix_hbm_f32(bx.ptr(), by.ptr(), pairs, d, n, m, n, m, k, out_ptr(out), bx.stream()))
-        return out
-    fn = lib.smx_cost_matrix_f32 if bx.bytes == 4 else lib.smx_cost_matrix_f64
-    check(fn(bx.ptr(), by.ptr(), pairs, d, n, m, k, out_ptr(out)))
-    return bx.wrap(out)
+    return bx.run((lib.smx_cost_matrix_f32, lib.smx_cost_matrix_f64), (bx.ptr(), by.ptr(), pairs, d, n, m, k, OUT),
+                  lib.smx_cost_matrix_hbm_f32, (bx.ptr(), by.ptr(), pairs, d, n, m, n, m, k, OUT, STREAM), lead_shape + (n, m),
+                  skip=pairs == 0, overwritten=True)
 
 
 def dtw(X, Y, metric: str = "euclidean", weights_add=(0, 0, 0), weights_mul=(1, 1, 1), subseq: bool = False):
@@ -103,17 +94,9 @@ def dtw(X, Y, metric: str = "euclidean", weights_add=(0, 0, 0), weights_mul=(1, 
     add, mul, sub = _weights(name, weights_add, "weights_add"), _weights(name, weights_mul, "weights_mul"), 1 if subseq else 0
     bx, by, lead_shape, pairs, d, n, m = _pairs(
         name, X, Y, lambda d, n, m: check((lib.smx_dtw_f64 if _wide(X) else lib.smx_dtw_f32)(None, None, 0, d, n, m, k, add, mul, sub, None, None)))
-    shapes = lead_shape + (n, m), lead_shape + (2, n + m - 1)
-    if pairs == 0:
-        return _zeros(bx, shapes[0]), _zeros(bx, shapes[1])
-    D, path = bx.empty(shapes[0], overwritten=True), bx.empty(shapes[1])
-    if bx.device:
-        with bx.device_guard():
-            check(lib.smx_dtw_hbm_f32(bx.ptr(), by.ptr(), pairs, d, n, m, n, m, k, add, mul, sub, out_ptr(D), out_ptr(path), bx.stream()))
-        return D, path
-    fn = lib.smx_dtw_f32 if bx.bytes == 4 else lib.smx_dtw_f64
-    check(fn(bx.ptr(), by.ptr(), pairs, d, n, m, k, add, mul, sub, out_ptr(D), out_ptr(path)))
-    return bx.wrap(D), bx.wrap(path)
+    return bx.run((lib.smx_dtw_f32, lib.smx_dtw_f64), (bx.ptr(), by.ptr(), pairs, d, n, m, k, add, mul, sub, OUT, OUT),
+                  lib.smx_dtw_hbm_f32, (bx.ptr(), by.ptr(), pairs, d, n, m, n, m, k, add, mul, sub, OUT, OUT, STREAM),
+                  [lead_shape + (n, m), lead_shape + (2, n + m - 1)], skip=pairs == 0, overwritten=(True, False))
 
 
 def dtw_distance(X, Y, metric: str = "euclidean", weights_add=(0, 0, 0), weights_mul=(1, 1, 1), subseq: bool = False):
@@ -123,17 +106,9 @@ def dtw_distance(X, Y, metric: str = "euclidean", weights_add=(0, 0, 0), weights
     k = _metric(name, metric)
     add, mul, sub = _weights(name, weights_add, "weights_add"), _weights(name, weights_mul, "weights_mul"), 1 if subseq else 0
     bx, by, lead_shape, pairs, d, n, m = _pairs(name, X, Y, lambda d, n, m: check(lib.smx_dtw_distance_f32(None, None, 0, d, n, m, k, add, mul, sub, None)))
-    shape = lead_shape + (1,)
-    if pairs == 0:
-        return _zeros(bx, shape)
-    out = bx.empty(shape)
-    if bx.device:
-        with bx.device_guard():
-            check(lib.smx_dtw_distance_hbm_f32(bx.ptr(), by.ptr(), pairs, d, n, m, n, m, k, add, mul, sub, out_ptr(out), bx.stream()))
-        return out
-    fn = lib.smx_dtw_distance_f32 if bx.bytes == 4 else lib.smx_dtw_distance_f64
-    check(fn(bx.ptr(), by.ptr(), pairs, d, n, m, k, add, mul, sub, out_ptr(out)))
-    return bx.wrap(out)
+    return bx.run((lib.smx_dtw_distance_f32, lib.smx_dtw_distance_f64), (bx.ptr(), by.ptr(), pairs, d, n, m, k, add, mul, sub, OUT),
+                  lib.smx_dtw_distance_hbm_f32, (bx.ptr(), by.ptr(), pairs, d, n, m, n, m, k, add, mul, sub, OUT, STREAM), lead_shape + (1,),
+                  skip=pairs == 0)
 
 
 def _wide(x) -> bool:

@@ -16,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._lib import lib
+from ._tensor import OUT, STREAM, Batch, Stateless, prod, refuse_device_float64
 
 
 def _spectrogram(op: str, s):
@@ -42,20 +42,10 @@ def _freqs(op: str, freqs):
     return f, C.c_void_p(f.ctypes.data), int(f.shape[0])
 
 
-def _run(op, b, lead_shape, bins, frames, host_fns, dev_fn, args_before, args_after):
-    lead = prod(lead_shape)
-    out = b.empty(lead_shape + (1, frames))
-    if b.device:
-        if b.bytes != 4:
-            raise _lib.Failure("%s: device-resident float64 spectrograms are not supported; pass a host array" % op)
-        if out.numel() > 0:
-            out.zero_()
-        with b.device_guard():
-            check(dev_fn(b.ptr(), lead, bins, frames, *args_before, *args_after, out_ptr(out), b.stream()))
-        return out
-    fn = host_fns[0] if b.bytes == 4 else host_fns[1]
-    check(fn(b.ptr(), lead, bins, frames, *args_before, *args_after, out_ptr(out)))
-    return b.wrap(out)
+def _run(op, b, lead_shape, bins, frames, host, device, args):
+    refuse_device_float64(op, b, "spectrograms are")
+    args = (b.ptr(), prod(lead_shape), bins, frames, *args, OUT)
+    return b.run(host, args, device, args + (STREAM,), lead_shape + (1, frames), prefill=True)
 
 
 def spectral_centroid(s, sample_rate: int, freqs=None):
@@ -64,7 +54,7 @@ def spectral_centroid(s, sample_rate: int, freqs=None):
     b, lead_shape, bins, frames = _spectrogram(op, s)
     f, fptr, nf = _freqs(op, freqs)
     return _run(op, b, lead_shape, bins, frames, (lib.smx_spectral_centroid_f32, lib.smx_spectral_centroid_f64),
-                lib.smx_spectral_centroid_f32_dev, (), (fptr, nf, int(sample_rate)))
+                lib.smx_spectral_centroid_f32_dev, (fptr, nf, int(sample_rate)))
 
 
 def spectral_bandwidth(s, sample_rate: int, p: float = 2.0, freqs=None, centroid=None):
@@ -92,7 +82,7 @@ def spectral_bandwidth(s, sample_rate: int, p: float = 2.0, freqs=None, centroid
         else:
             cptr = C.c_void_p(1)   # never dereferenced: the shape check fails first and words the error
     return _run(op, b, lead_shape, bins, frames, (lib.smx_spectral_bandwidth_f32, lib.smx_spectral_bandwidth_f64),
-                lib.smx_spectral_bandwidth_f32_dev, (float(p),), (fptr, nf, cptr, c_rows, c_frames, int(sample_rate)))
+                lib.smx_spectral_bandwidth_f32_dev, (float(p), fptr, nf, cptr, c_rows, c_frames, int(sample_rate)))
 
 
 def spectral_rolloff(s, sample_rate: int, roll_percent: float = 0.85, freqs=None):
@@ -101,7 +91,7 @@ def spectral_rolloff(s, sample_rate: int, roll_percent: float = 0.85, freqs=None
     b, lead_shape, bins, frames = _spectrogram(op, s)
     f, fptr, nf = _freqs(op, freqs)
     return _run(op, b, lead_shape, bins, frames, (lib.smx_spectral_rolloff_f32, lib.smx_spectral_rolloff_f64),
-                lib.smx_spectral_rolloff_f32_dev, (float(roll_percent),), (fptr, nf, int(sample_rate)))
+                lib.smx_spectral_rolloff_f32_dev, (float(roll_percent), fptr, nf, int(sample_rate)))
 
 
 def spectral_flatness(s, amin: float = 1e-10, power: float = 2.0):
@@ -109,7 +99,7 @@ def spectral_flatness(s, amin: float = 1e-10, power: float = 2.0):
     op = "spectral_flatness"
     b, lead_shape, bins, frames = _spectrogram(op, s)
     return _run(op, b, lead_shape, bins, frames, (lib.smx_spectral_flatness_f32, lib.smx_spectral_flatness_f64),
-                lib.smx_spectral_flatness_f32_dev, (float(amin), float(power)), ())
+                lib.smx_spectral_flatness_f32_dev, (float(amin), float(power)))
 
 
 # ---- memoryless Pipeline stages (spectral.ml:257-284): every chunk-independent parameter is validated where the
@@ -139,7 +129,6 @@ def spectral_centroid_stage(sample_rate: int, freqs=None):
     op = "spectral_centroid_stage"
     _check_sample_rate(op, sample_rate)
     _check_freqs_rank(op, freqs)
-    from ._tensor import Stateless
     return Stateless(lambda s: spectral_centroid(s, sample_rate=sample_rate, freqs=freqs))
 
 
@@ -149,7 +138,6 @@ def spectral_bandwidth_stage(sample_rate: int, p: float = 2.0, freqs=None):
         raise _lib.InvalidArgument("%s: cannot raise deviations to the power %s (p must be finite and positive)" % (op, _g(p)))
     _check_sample_rate(op, sample_rate)
     _check_freqs_rank(op, freqs)
-    from ._tensor import Stateless
     return Stateless(lambda s: spectral_bandwidth(s, sample_rate=sample_rate, p=p, freqs=freqs))
 
 
@@ -160,7 +148,6 @@ def spectral_rolloff_stage(sample_rate: int, roll_percent: float = 0.85, freqs=N
                                    "and 1)" % (op, _g(roll_percent)))
     _check_sample_rate(op, sample_rate)
     _check_freqs_rank(op, freqs)
-    from ._tensor import Stateless
     return Stateless(lambda s: spectral_rolloff(s, sample_rate=sample_rate, roll_percent=roll_percent, freqs=freqs))
 
 
@@ -170,5 +157,4 @@ def spectral_flatness_stage(amin: float = 1e-10, power: float = 2.0):
         raise _lib.InvalidArgument("%s: cannot floor the spectrum at %s (amin must be finite and positive)" % (op, _g(amin)))
     if not _finite_positive(power):
         raise _lib.InvalidArgument("%s: cannot raise magnitudes to the power %s (power must be finite and positive)" % (op, _g(power)))
-    from ._tensor import Stateless
     return Stateless(lambda s: spectral_flatness(s, amin=amin, power=power))

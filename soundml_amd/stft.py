@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from ._tensor import Batch, out_ptr, prod
+from ._tensor import OUT, STREAM, Batch, prod
 
 
 class Config:
@@ -148,28 +148,17 @@ def _range(c: Config, x, p0, p1, power, op):
         p0, p1 = 0, total
     complex_ = power is None
     count = max(0, p1 - p0)
-    out = b.empty(lead_shape + (c.bins, count), complex_=complex_, overwritten=True)
-    sfx = "f32" if b.bytes == 4 else "f64"
-    if b.device:
-        with b.device_guard():
-            if complex_:
-                fn = getattr(lib, "smx_stft_transform_range_%s_dev" % sfx)
-                check(fn(c._h, b.ptr(), lead, n, n, p0, p1, out_ptr(out), b.stream()))
-            else:
-                fn = getattr(lib, "smx_stft_power_range_%s_dev" % sfx)
-                check(fn(c._h, b.ptr(), lead, n, n, p0, p1, float(power), out_ptr(out), b.stream()))
-        return out
     if complex_:
-        fn = getattr(lib, "smx_stft_transform_range_%s" % sfx)
-        check(fn(c._h, b.ptr(), lead, n, p0, p1, out_ptr(out)))
+        host, span, tail = (lib.smx_stft_transform_range_f32, lib.smx_stft_transform_range_f64), (p0, p1), (OUT,)
+        device = (lib.smx_stft_transform_range_f32_dev, lib.smx_stft_transform_range_f64_dev)
     else:
-        if (p0, p1) == (0, total):
-            fn = getattr(lib, "smx_stft_power_spectrum_%s" % sfx)
-            check(fn(c._h, b.ptr(), lead, n, float(power), out_ptr(out)))
+        tail, device = (float(power), OUT), (lib.smx_stft_power_range_f32_dev, lib.smx_stft_power_range_f64_dev)
+        if (p0, p1) == (0, total):                       # the whole clip has a host entry of its own
+            host, span = (lib.smx_stft_power_spectrum_f32, lib.smx_stft_power_spectrum_f64), ()
         else:
-            fn = getattr(lib, "smx_stft_power_range_%s" % sfx)
-            check(fn(c._h, b.ptr(), lead, n, p0, p1, float(power), out_ptr(out)))
-    return b.wrap(out)
+            host, span = (lib.smx_stft_power_range_f32, lib.smx_stft_power_range_f64), (p0, p1)
+    return b.run(host, (c._h, b.ptr(), lead, n, *span, *tail), device, (c._h, b.ptr(), lead, n, n, p0, p1, *tail, STREAM),
+                 lead_shape + (c.bins, count), complex_=complex_, overwritten=True)
 
 
 def transform(c: Config, x):
