@@ -145,6 +145,10 @@ int smx_get_devices(int *devices, int capacity, int *n);
 int smx_shard_clip_range(int64_t total_clips, int64_t shards, int64_t shard, int64_t *lo, int64_t *hi);
 /* diagnostics (tests of the per-device staging): the most staged uploads / downloads that were ever in flight at once */
 int smx_debug_staging_peak(int *uploads, int *downloads, int reset);
+/* diagnostics (tests of the launch extents; no device needed): one launch holds at most 2^32 - 1 work-items and 2^31 - 1 workgroups
+ * on its first grid axis, so a batch whose clips each take `tiles_per_clip` workgroups of `threads` goes this many clips at a time
+ * (0: a single clip does not fit, which the entry point refuses with "too many ... for one launch") */
+int64_t smx_debug_clips_per_launch(int64_t tiles_per_clip, int threads);
 int smx_set_interior(int interior);    /* SMX_INTERIOR_*, process-wide default for f32 audio */
 /* Scratch arrays (Griffin-Lim's spectra, scratch spectrograms, small tables) come from a stream-ordered memory pool
  * that the library creates for itself on each device (the process-wide default pool is never touched); it keeps up to

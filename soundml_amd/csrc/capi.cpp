@@ -374,6 +374,7 @@ int smx_shard_clip_range(int64_t total_clips, int64_t shards, int64_t shard, int
 int smx_debug_staging_peak(int *uploads, int *downloads, int reset) {
   return guarded([&] { staging_peak(uploads, downloads, reset != 0); });
 }
+int64_t smx_debug_clips_per_launch(int64_t tiles_per_clip, int threads) { return clips_per_launch(tiles_per_clip, threads); }
 
 int smx_set_scratch_retention(int64_t bytes) {
   return guarded([&] {

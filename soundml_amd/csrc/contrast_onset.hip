@@ -274,11 +274,6 @@ __global__ void __launch_bounds__(256) flux_kernel(FluxArgs a) {
   reinterpret_cast<T *>(a.out)[clip * a.frames + t] = (T)z;
 }
 
-unsigned tiles(const char *what, int64_t lead, int64_t per_clip) {
-  if (lead * per_clip > 2147483647LL) throw Failure(format("%s: too many frame tiles for one launch", what));
-  return (unsigned)(lead * per_clip);
-}
-
 // ---- the band plan (contrast.ml:50-142), host integers and float64 as the reference writes them -----------------------------
 double rint_even(double x) {      // contrast.ml:52-58
   const double fl = std::floor(x), d = x - fl;
@@ -372,13 +367,13 @@ void contrast_apply_dev(const char *fn, const std::vector<Band> &plan, const Con
     a.valley = reinterpret_cast<double *>(scratch.as<unsigned char>() + 32);
     a.peak = a.valley + total;
   }
-  const dim3 grid(tiles(fn, lead, a.ftiles), (unsigned)a.rows);
+  const dim3 grid(grid_x(fn, "frame tiles", lead * a.ftiles, 64), (unsigned)a.rows);
   if (elem_bytes == 8) SMX_LAUNCH(contrast_kernel<double>, grid, dim3(64), 0, stream, a);
   else SMX_LAUNCH(contrast_kernel<float>, grid, dim3(64), 0, stream, a);
   SMX_HIP_CHECK(hipGetLastError());
   if (means) {
     launch_max_key<double>(a.valley, total, 2, a.keys, stream);          // valley and peak lie one behind the other
-    const unsigned blocks = tiles(fn, 1, (total + 255) / 256);
+    const unsigned blocks = grid_x(fn, "frame tiles", (total + 255) / 256, 256);
     if (elem_bytes == 8)
       SMX_LAUNCH(contrast_db_kernel<double>, dim3(blocks), dim3(256), 0, stream, a.valley, a.peak, a.keys, (double *)d_out, total);
     else
@@ -480,10 +475,19 @@ void check_lag(const char *fn, int64_t lag) {               // onset.ml:29-34
 template <bool LOG>
 void launch_flux(const char *fn, FluxArgs a, int elem_bytes, hipStream_t stream) {
   a.ftiles = (a.frames + 255) / 256;
-  const dim3 grid(tiles(fn, a.lead, a.ftiles));
-  if (elem_bytes == 8) SMX_LAUNCH((flux_kernel<double, LOG>), grid, dim3(256), 0, stream, a);
-  else SMX_LAUNCH((flux_kernel<float, LOG>), grid, dim3(256), 0, stream, a);
-  SMX_HIP_CHECK(hipGetLastError());
+  // clip range by clip range (DESIGN.md "Launch extents"); the LOG clamp's maximum is the whole tensor's and stays the caller's
+  const int64_t lead = a.lead, per_launch = std::max<int64_t>(1, clips_per_launch(a.ftiles, 256));
+  const char *s = reinterpret_cast<const char *>(a.s);
+  char *out = reinterpret_cast<char *>(a.out);
+  for (int64_t c0 = 0; c0 < lead; c0 += per_launch) {
+    a.lead = std::min(per_launch, lead - c0);
+    a.s = s + c0 * a.bins * a.frames * elem_bytes;
+    a.out = out + c0 * a.frames * elem_bytes;
+    const dim3 grid(grid_x(fn, "frame tiles", a.lead * a.ftiles, 256));
+    if (elem_bytes == 8) SMX_LAUNCH((flux_kernel<double, LOG>), grid, dim3(256), 0, stream, a);
+    else SMX_LAUNCH((flux_kernel<float, LOG>), grid, dim3(256), 0, stream, a);
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 // the one-chunk state_step (onset.ml:82-122) with an empty carry: decibels in, no clamp, no shift

@@ -244,8 +244,8 @@ void launch_cqt_project(const CqtProjectJob &job) {
   a.ftiles = (job.frames + kFrameTile - 1) / kFrameTile;
   a.mode = (int)job.mode; a.power = job.power; a.out = job.out;
   const int64_t btiles = (job.count + kBinTile - 1) / kBinTile;
-  if (a.ftiles > 2147483647LL / job.lead || btiles > 65535) throw Failure("cqt: too many tiles for one launch");
-  SMX_LAUNCH(cqt_project_kernel, dim3((unsigned)(job.lead * a.ftiles), (unsigned)btiles), dim3(256), 0, job.stream, a);
+  if (btiles > kMaxGridYZ) throw Failure("cqt: too many tiles for one launch");
+  SMX_LAUNCH(cqt_project_kernel, dim3(grid_x("cqt", "tiles", job.lead * a.ftiles, 256), (unsigned)btiles), dim3(256), 0, job.stream, a);
   SMX_HIP_CHECK(hipGetLastError());
 }
 

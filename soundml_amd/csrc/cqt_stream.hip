@@ -201,8 +201,7 @@ void append(smx_cqt_kernel &k, const std::vector<const float *> &src, const std:
   }
   if (jobs == 0) return;
   a.xtiles = ceil_div(longest, 256);
-  if (a.xtiles > 2147483647LL / k.channels) throw Failure("cqt_kernel: too many channels for one launch");
-  SMX_LAUNCH(cqt_stream_append_kernel, dim3((unsigned)(a.xtiles * k.channels), (unsigned)jobs), dim3(256), 0, stream, a);
+  SMX_LAUNCH(cqt_stream_append_kernel, dim3(grid_x("cqt_kernel", "channels", a.xtiles * k.channels, 256), (unsigned)jobs), dim3(256), 0, stream, a);
   SMX_HIP_CHECK(hipGetLastError());
 }
 
@@ -226,7 +225,7 @@ void project(smx_cqt_kernel &k, const std::vector<int64_t> &target, hipStream_t 
     job.cap = s.cap; job.seen = s.seen; job.n_fft = o.n_fft; job.hop = o.hop; job.frame0 = s.produced;
     job.gain = s.gain; job.pad_value = s.pad_value;
     const int64_t ftiles = ceil_div(k.channels * nframes, kCqtFrameTile), btiles = ceil_div(o.count, kCqtBinTile);
-    if (ftiles * btiles > 2147483647LL - tiles) throw Failure("cqt_kernel: too many tiles for one launch");
+    grid_x("cqt_kernel", "tiles", tiles + ftiles * btiles, 256);   // (before the int fields below take their share of it)
     job.count = (int)o.count; job.first = (int)o.first; job.nframes = (int)nframes;
     job.ftiles = (int)ftiles; job.tile0 = (int)tiles;
     tiles += ftiles * btiles;
@@ -235,7 +234,7 @@ void project(smx_cqt_kernel &k, const std::vector<int64_t> &target, hipStream_t 
   if (a.njobs == 0) return;
   a.channels = (int)k.channels; a.pad = c.pad; a.mode = (int)k.mode; a.power = k.power;
   a.n_bins = c.n_bins; a.ring_cap = k.ring_cap; a.ring = k.ring;
-  SMX_LAUNCH(cqt_stream_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a);
+  SMX_LAUNCH(cqt_stream_project_kernel, dim3(grid_x("cqt_kernel", "tiles", tiles, 256)), dim3(256), 0, stream, a);
   SMX_HIP_CHECK(hipGetLastError());
 }
 
@@ -243,13 +242,13 @@ void project(smx_cqt_kernel &k, const std::vector<int64_t> &target, hipStream_t 
 int64_t emit(smx_cqt_kernel &k, int64_t upto, void *d_out, int64_t out_stride, hipStream_t stream) {
   const int64_t columns = upto - k.emitted;
   if (columns <= 0) return 0;
-  const int64_t rows = k.channels * k.config->n_bins, blocks = ceil_div(rows * columns, 256);
-  if (blocks > 2147483647LL) throw Failure("cqt_kernel: too many columns for one launch");
+  const int64_t rows = k.channels * k.config->n_bins;
+  const unsigned blocks = grid_x("cqt_kernel", "columns", ceil_div(rows * columns, 256), 256);
   if (k.mode == OUT_COMPLEX)
-    SMX_LAUNCH(cqt_stream_emit_kernel<float2>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float2 *)k.ring, k.ring_cap, k.emitted,
+    SMX_LAUNCH(cqt_stream_emit_kernel<float2>, dim3(blocks), dim3(256), 0, stream, (const float2 *)k.ring, k.ring_cap, k.emitted,
                columns, rows, (float2 *)d_out, out_stride);
   else
-    SMX_LAUNCH(cqt_stream_emit_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float *)k.ring, k.ring_cap, k.emitted,
+    SMX_LAUNCH(cqt_stream_emit_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float *)k.ring, k.ring_cap, k.emitted,
                columns, rows, (float *)d_out, out_stride);
   SMX_HIP_CHECK(hipGetLastError());
   k.emitted = upto;

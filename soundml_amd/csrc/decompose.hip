@@ -428,18 +428,12 @@ void check_stride(const char *fn, const char *what, int64_t stride, int64_t leas
   if (stride < least) throw InvalidArgument(format("%s: %s is %lld (at least %lld)", fn, what, (long long)stride, (long long)least));
 }
 
-unsigned grid_of(const char *fn, int64_t threads, int per) {
-  const int64_t blocks = (threads + per - 1) / per;
-  if (blocks > 2147483647LL) throw Failure(format("%s: too many cells for one launch", fn));
-  return (unsigned)blocks;
-}
-
 bool takes_tiles(int64_t K, int elem_bytes) { return elem_bytes == 4 && K <= kTileK && !fast_path_disabled(); }
 
 template <bool KL>
 void launch_tiles_of(const char *fn, const Args &a, int side, int64_t clips, hipStream_t stream) {
   const int64_t blocks = side == 0 ? (a.T + 31) / 32 : (a.F + 31) / 32;
-  const unsigned grid = grid_of(fn, clips * blocks, 1);
+  const unsigned grid = grid_x(fn, "cells", clips * blocks, 64);
   if (side == 0) {
     if (a.K <= 32) SMX_LAUNCH((h_tile_kernel<1, KL>), dim3(grid), dim3(64), 0, stream, a, blocks);
     else SMX_LAUNCH((h_tile_kernel<2, KL>), dim3(grid), dim3(64), 0, stream, a, blocks);
@@ -453,10 +447,10 @@ void launch_tiles_of(const char *fn, const Args &a, int side, int64_t clips, hip
 template <typename T>
 void update_general(const char *fn, const Args &a, int side, int64_t clips, hipStream_t stream) {
   const int64_t cells = side == 0 ? a.K * a.T : a.F * a.K;
-  if (a.beta == SMX_NMF_KULLBACK_LEIBLER) SMX_LAUNCH((ratio_kernel<T>), dim3(grid_of(fn, clips * a.F * a.T, 256)), dim3(256), 0, stream, a, clips);
-  else SMX_LAUNCH((denom_kernel<T>), dim3(grid_of(fn, clips * cells, 256)), dim3(256), 0, stream, a, side, clips);
+  if (a.beta == SMX_NMF_KULLBACK_LEIBLER) SMX_LAUNCH((ratio_kernel<T>), dim3(grid_x(fn, "cells", (clips * a.F * a.T + 255) / 256, 256)), dim3(256), 0, stream, a, clips);
+  else SMX_LAUNCH((denom_kernel<T>), dim3(grid_x(fn, "cells", (clips * cells + 255) / 256, 256)), dim3(256), 0, stream, a, side, clips);
   SMX_HIP_CHECK(hipGetLastError());
-  SMX_LAUNCH((update_kernel<T>), dim3(grid_of(fn, clips * cells, 256)), dim3(256), 0, stream, a, side, clips);
+  SMX_LAUNCH((update_kernel<T>), dim3(grid_x(fn, "cells", (clips * cells + 255) / 256, 256)), dim3(256), 0, stream, a, side, clips);
   SMX_HIP_CHECK(hipGetLastError());
 }
 
@@ -481,7 +475,7 @@ void nmf_dev(const char *fn, const Shape &s, int elem_bytes, int beta, int64_t n
     a.V = (const char *)d_V + c0 * vs * eb, a.W = (char *)d_W + c0 * ws * eb, a.H = (char *)d_H + c0 * hs * eb;
     a.G = base, a.R = kl ? base + step * g_bytes : nullptr, a.D = kl ? nullptr : base + step * g_bytes;
     a.vs = vs, a.vp = vp, a.ws = ws, a.hs = hs, a.ds = ds, a.F = s.F, a.T = s.T, a.K = s.K, a.beta = beta;
-    const unsigned gram_grid = grid_of(fn, nc * s.K * (kl ? 1 : s.K + 1), 256);
+    const unsigned gram_grid = grid_x(fn, "cells", (nc * s.K * (kl ? 1 : s.K + 1) + 255) / 256, 256);
     for (int64_t it = 0; it < n_iter; ++it) {
       for (int side = 0; side < (with_w ? 2 : 1); ++side) {
         // G of the factor that stays fixed in this update
@@ -503,7 +497,7 @@ void nmf_dev(const char *fn, const Shape &s, int elem_bytes, int beta, int64_t n
 
 void copy_factor(void *dst, int64_t dst_stride, const void *src, int64_t src_stride, int64_t cells, int64_t clips, int elem_bytes, hipStream_t stream) {
   if (dst == src && dst_stride == src_stride) return;
-  const unsigned grid = grid_of("nmf", clips * cells, 256);
+  const unsigned grid = grid_x("nmf", "cells", (clips * cells + 255) / 256, 256);
   if (elem_bytes == 4) SMX_LAUNCH((copy_kernel<float>), dim3(grid), dim3(256), 0, stream, (const float *)src, src_stride, (float *)dst, dst_stride, cells, clips);
   else SMX_LAUNCH((copy_kernel<double>), dim3(grid), dim3(256), 0, stream, (const double *)src, src_stride, (double *)dst, dst_stride, cells, clips);
   SMX_HIP_CHECK(hipGetLastError());
@@ -553,7 +547,7 @@ void reconstruct_dev(const char *fn, const Shape &s, int elem_bytes, const Mask 
                      void *d_out, int64_t os, int64_t op, hipStream_t stream) {
   ReconstructArgs a{};
   a.W = d_W, a.H = d_H, a.out = d_out, a.ws = ws, a.hs = hs, a.os = os, a.op = op, a.F = s.F, a.T = s.T, a.K = s.K, a.as_mask = as_mask, a.mask = mask;
-  const unsigned grid = grid_of(fn, clips * s.F * s.T, 256);
+  const unsigned grid = grid_x(fn, "cells", (clips * s.F * s.T + 255) / 256, 256);
   if (elem_bytes == 4) SMX_LAUNCH((reconstruct_kernel<float>), dim3(grid), dim3(256), 0, stream, a, clips);
   else SMX_LAUNCH((reconstruct_kernel<double>), dim3(grid), dim3(256), 0, stream, a, clips);
   SMX_HIP_CHECK(hipGetLastError());
@@ -601,7 +595,7 @@ void divergence_dev(const char *fn, const Shape &s, int elem_bytes, int beta, co
   DivergenceArgs a{};
   a.V = d_V, a.W = d_W, a.H = d_H, a.rows = scratch.as<double>(), a.out = d_out;
   a.vs = vs, a.vp = vp, a.ws = ws, a.hs = hs, a.F = s.F, a.T = s.T, a.K = s.K, a.beta = beta;
-  const unsigned rows_grid = grid_of(fn, clips * s.F, 64), end_grid = grid_of(fn, clips, 64);
+  const unsigned rows_grid = grid_x(fn, "cells", (clips * s.F + 63) / 64, 64), end_grid = grid_x(fn, "cells", (clips + 63) / 64, 64);
   if (elem_bytes == 4) {
     SMX_LAUNCH((divergence_rows_kernel<float>), dim3(rows_grid), dim3(64), 0, stream, a, clips);
     SMX_LAUNCH((divergence_end_kernel<float>), dim3(end_grid), dim3(64), 0, stream, a, clips);

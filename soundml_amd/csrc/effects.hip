@@ -226,8 +226,7 @@ void launch_typed(const PvocJob &job, PvocArgs a) {
     return;
   }
   const int64_t per_signal = (job.bins + kBins - 1) / kBins;
-  if (per_signal > 2147483647LL / job.lead) throw Failure("phase_vocoder: too many bin blocks for one launch");
-  SMX_LAUNCH(pvoc_independent_kernel<Z>, dim3((unsigned)(per_signal * job.lead)), dim3(kThreads), 0, job.stream, a);
+  SMX_LAUNCH(pvoc_independent_kernel<Z>, dim3(grid_x("phase_vocoder", "bin blocks", per_signal * job.lead, kThreads)), dim3(kThreads), 0, job.stream, a);
   SMX_HIP_CHECK(hipGetLastError());
 }
 

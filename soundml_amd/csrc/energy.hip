@@ -276,19 +276,29 @@ void launch_energy(const char *fn, EnergyArgs a, hipStream_t stream) {
   a.tile_frames = tile_frames(a.fl, a.hop, (int)sizeof(T));
   const int64_t per_tile = a.tile_frames ? a.tile_frames : 4;
   a.tiles = (a.frames + per_tile - 1) / per_tile;
-  if (a.lead * a.tiles > 2147483647LL) throw Failure(format("%s: too many frame tiles for one launch", fn));
-  const dim3 grid((unsigned)(a.lead * a.tiles));
+  // clip range by clip range where the batch exceeds one launch (DESIGN.md "Launch extents"); the clips are independent
+  const int64_t lead = a.lead, per_launch = std::max<int64_t>(1, clips_per_launch(a.tiles, 256));
+  const char *x = reinterpret_cast<const char *>(a.x);
+  char *out = reinterpret_cast<char *>(a.out);
   if (a.tile_frames) {
-    constexpr int64_t kVec = 16 / sizeof(T);
     a.nfull = (int)(a.fl / a.hop);
     a.rest = (int)(a.fl - a.nfull * a.hop);
-    const int64_t cap = (kVec - 1 + (a.tile_frames - 1) * a.hop + a.fl + kVec - 1) / kVec;
-    const size_t lds = (size_t)cap * 16 + (size_t)(a.tile_frames + a.nfull) * 16;
-    SMX_LAUNCH((energy_frames_kernel<T, OP>), grid, dim3(256), lds, stream, a);
-  } else {
-    SMX_LAUNCH((energy_frames_general_kernel<T, OP>), grid, dim3(256), 0, stream, a);
   }
-  SMX_HIP_CHECK(hipGetLastError());
+  for (int64_t c0 = 0; c0 < lead; c0 += per_launch) {
+    a.lead = std::min(per_launch, lead - c0);
+    a.x = x + c0 * a.x_stride * (int64_t)sizeof(T);
+    a.out = out + c0 * a.frames * (int64_t)sizeof(T);
+    const dim3 grid(grid_x(fn, "frame tiles", a.lead * a.tiles, 256));
+    if (a.tile_frames) {
+      constexpr int64_t kVec = 16 / sizeof(T);
+      const int64_t cap = (kVec - 1 + (a.tile_frames - 1) * a.hop + a.fl + kVec - 1) / kVec;
+      const size_t lds = (size_t)cap * 16 + (size_t)(a.tile_frames + a.nfull) * 16;
+      SMX_LAUNCH((energy_frames_kernel<T, OP>), grid, dim3(256), lds, stream, a);
+    } else {
+      SMX_LAUNCH((energy_frames_general_kernel<T, OP>), grid, dim3(256), 0, stream, a);
+    }
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 // frames [0, count) of rows extended by `border` virtual positions on each side; the parameters are the caller's to check
@@ -397,16 +407,21 @@ void of_spectrogram_dev(int64_t fl, const void *d_s, int elem_bytes, int64_t lea
   if (lead == 0 || frames == 0) return;
   if (!d_s || !d_out) throw Failure("rms_of_spectrogram: null device pointer");
   const int64_t ftiles = (frames + 255) / 256;
-  if (lead * ftiles > 2147483647LL) throw Failure("rms_of_spectrogram: too many frame tiles for one launch");
-  const dim3 grid((unsigned)(lead * ftiles));
   const int even = fl % 2 == 0 ? 1 : 0;
-  if (elem_bytes == 8)
-    SMX_LAUNCH(rms_of_spectrogram_kernel<double>, grid, dim3(256), 0, stream, (const double *)d_s, (double *)d_out, bins, frames, ftiles, even,
-               (double)fl);
-  else
-    SMX_LAUNCH(rms_of_spectrogram_kernel<float>, grid, dim3(256), 0, stream, (const float *)d_s, (float *)d_out, bins, frames, ftiles, even,
-               (double)fl);
-  SMX_HIP_CHECK(hipGetLastError());
+  const int64_t per_launch = std::max<int64_t>(1, clips_per_launch(ftiles, 256));   // clip range by clip range (DESIGN.md "Launch extents")
+  for (int64_t c0 = 0; c0 < lead; c0 += per_launch) {
+    const int64_t nc = std::min(per_launch, lead - c0);
+    const dim3 grid(grid_x("rms_of_spectrogram", "frame tiles", nc * ftiles, 256));
+    const char *s = (const char *)d_s + c0 * bins * frames * elem_bytes;
+    char *out = (char *)d_out + c0 * frames * elem_bytes;
+    if (elem_bytes == 8)
+      SMX_LAUNCH(rms_of_spectrogram_kernel<double>, grid, dim3(256), 0, stream, (const double *)s, (double *)out, bins, frames, ftiles, even,
+                 (double)fl);
+    else
+      SMX_LAUNCH(rms_of_spectrogram_kernel<float>, grid, dim3(256), 0, stream, (const float *)s, (float *)out, bins, frames, ftiles, even,
+                 (double)fl);
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 void of_spectrogram_host(int64_t fl, const void *s, int elem_bytes, int64_t lead, int64_t bins, int64_t frames, void *out) {

@@ -877,8 +877,7 @@ void fir_apply_window_dev(const smx_fir_plan &p, const float *d_x, int64_t chann
     da.taps = (int)p.taps;
     for (int64_t k = 0; k < p.taps; ++k) da.h[k] = (float)p.h[(size_t)k];
     const int64_t tiles = (n_out + 2047) / 2048;
-    if (tiles > 0x7fffffff) throw Failure("fir_apply: too many blocks for one launch");
-    SMX_LAUNCH(fir_direct_kernel, dim3((unsigned)tiles, (unsigned)channels), dim3(256), 0, stream, da);
+    SMX_LAUNCH(fir_direct_kernel, dim3(grid_x("fir_apply", "blocks", tiles, 256), (unsigned)channels), dim3(256), 0, stream, da);
     SMX_HIP_CHECK(hipGetLastError());
     return;
   }
@@ -888,13 +887,13 @@ void fir_apply_window_dev(const smx_fir_plan &p, const float *d_x, int64_t chann
   a.blocks_per_channel = (out_shift + n_out + a.step - 1) / a.step;
   a.channels = channels;
   const int64_t grid = channels * a.blocks_per_channel;
-  if (grid > 0x7fffffff) throw Failure("fir_apply: too many blocks for one launch");
   const bool aligned = x_stride % 2 == 0 && y_stride % 2 == 0 && out_shift % 2 == 0 &&
                        reinterpret_cast<uintptr_t>(d_x) % 8 == 0 && reinterpret_cast<uintptr_t>(d_y) % 8 == 0;
-  auto launch = [&](auto kernel, int64_t workgroups, int threads, size_t lds) {
+  auto launch = [&](auto kernel, int64_t count, int threads, size_t lds) {
+    const unsigned workgroups = grid_x("fir_apply", "blocks", count, threads);
     SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SMX_LAUNCH(kernel, dim3((unsigned)workgroups), dim3(threads), lds, stream, a);
+    SMX_LAUNCH(kernel, dim3(workgroups), dim3(threads), lds, stream, a);
   };
   const int threads = (int)(p.nfft / 32);                        // M / 16
   const size_t lds = (size_t)(p.nfft / 2) * sizeof(float2);      // M points
@@ -1165,12 +1164,12 @@ void poly_run(const smx_resample_stage &s, const float *d_x, int64_t x0, int64_t
   a.h = t.h;
   a.tw = t.tw;
   const int64_t grid = channels * pairs;
-  if (grid > 0x7fffffff) throw Failure("resample_stage: too many blocks for one launch");
   const size_t lds = 2 * (size_t)s.nfft * sizeof(float2);
   const bool up = s.l > 1;
   auto launch = [&](auto kernel, int threads) {
+    const unsigned blocks = grid_x("resample_stage", "blocks", grid, threads);
     SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SMX_LAUNCH(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
+    SMX_LAUNCH(kernel, dim3(blocks), dim3(threads), lds, stream, a);
   };
   switch (s.log2n) {
     case 10: up ? launch(smx::resample_poly_kernel<10, true>, 64) : launch(smx::resample_poly_kernel<10, false>, 64); break;

@@ -100,13 +100,18 @@ void launch_gl_narrow(const double *src, float *dst, int64_t total, hipStream_t 
 void launch_gl_to_frame_major(const void *src, void *dst, int64_t lead, int64_t bins, int64_t frames, int64_t rows, int64_t pitch, int elem_bytes,
                               hipStream_t stream) {
   if (lead <= 0 || bins <= 0 || frames <= 0) return;
-  if (lead > 65535) throw Failure("griffin_lim: too many clips for the frame-major transposition");
-  const dim3 grid((unsigned)((frames + 31) / 32), (unsigned)((bins + 31) / 32), (unsigned)lead);
-  if (elem_bytes == 8)
-    SMX_LAUNCH(gl_to_frame_major_kernel<float2>, grid, dim3(256), 0, stream, (const float2 *)src, (float2 *)dst, bins, frames, rows, pitch);
-  else
-    SMX_LAUNCH(gl_to_frame_major_kernel<float>, grid, dim3(256), 0, stream, (const float *)src, (float *)dst, bins, frames, rows, pitch);
-  SMX_HIP_CHECK(hipGetLastError());
+  if ((bins + 31) / 32 > kMaxGridYZ) throw Failure("griffin_lim: too many bins for the frame-major transposition");
+  const unsigned ftiles = grid_x("griffin_lim", "frame tiles", (frames + 31) / 32, 256);
+  for (int64_t c0 = 0; c0 < lead; c0 += kMaxGridYZ) {            // a clip per blockIdx.z: 65535 at a time (DESIGN.md "Launch extents")
+    const dim3 grid(ftiles, (unsigned)((bins + 31) / 32), (unsigned)std::min(kMaxGridYZ, lead - c0));
+    const char *s = (const char *)src + c0 * bins * frames * elem_bytes;
+    char *d = (char *)dst + c0 * rows * pitch * elem_bytes;
+    if (elem_bytes == 8)
+      SMX_LAUNCH(gl_to_frame_major_kernel<float2>, grid, dim3(256), 0, stream, (const float2 *)s, (float2 *)d, bins, frames, rows, pitch);
+    else
+      SMX_LAUNCH(gl_to_frame_major_kernel<float>, grid, dim3(256), 0, stream, (const float *)s, (float *)d, bins, frames, rows, pitch);
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 void launch_gl_init(const void *phase, void *angles, int64_t total, int elem_bytes, hipStream_t stream) {
@@ -218,7 +223,7 @@ void griffin_lim_dev(const smx_stft_config &c, const void *d_s, int elem_bytes, 
   auto fm_analysis_job = [&](const void *x, void *out) {
     return stft_job(c, x, 4, lead, natural, natural, 0, frames, OUT_COMPLEX, 0.0, out, stream);
   };
-  if (folded && elem_bytes == 4 && env_flag("SMX_GL_FRAME_MAJOR") != 0 && c.frames(natural) == frames && lead <= 65535) {   // (the transposition's grid: a clip per blockIdx.z)
+  if (folded && elem_bytes == 4 && env_flag("SMX_GL_FRAME_MAJOR") != 0 && c.frames(natural) == frames && lead <= kMaxGridYZ) {   // (the fft-2048 analysis takes at most 65535 clips: fast_eligible)
     IstftJob probe = make_job(nullptr, 0, 0, nullptr, natural);
     probe.fm_pitch = fm_pitch;
     probe.fm_rows = fm_rows;

@@ -313,7 +313,7 @@ void launch_hpss(const HpssJob &job) {
   const int64_t cells = job.lead * job.bins * job.frames;
   const bool fast = hpss_takes_fast_path(job);
   const int64_t blocks = fast ? job.lead * ((job.frames + TILE_F - 1) / TILE_F) * ((job.bins + TILE_B - 1) / TILE_B) : (cells + 255) / 256;
-  if (blocks > 0x7FFFFFFFll) throw Failure("hpss: the spectrogram has too many cells for one launch (pass it in slices of its leading axes)");
+  if (blocks > clips_per_launch(1, 256)) throw Failure("hpss: the spectrogram has too many cells for one launch (pass it in slices of its leading axes)");
   HpssArgs a;
   a.src = job.s;
   a.mag = nullptr;

@@ -400,16 +400,10 @@ void steady_state(const IirCore &core, double *zi) {
   }
 }
 
-int64_t blocks_of(const char *fn, int64_t count, int64_t per) {
-  const int64_t blocks = (count + per - 1) / per;
-  if (blocks > 2147483647LL) throw Failure(format("%s: too many workgroups for one launch", fn));
-  return blocks;
-}
-
 template <int S>
 void launch_general(const char *fn, const IirCore &core, const IirIo &io, double *st, int64_t lead, int64_t i0, int64_t i1, int pos0,
                     hipStream_t stream) {
-  SMX_LAUNCH((iir_general_kernel<S>), dim3((unsigned)blocks_of(fn, lead, 64)), dim3(64), 0, stream, core.coef, io, core.device_matrix(), st, lead,
+  SMX_LAUNCH((iir_general_kernel<S>), dim3(grid_x(fn, "workgroups", (lead + 63) / 64, 64)), dim3(64), 0, stream, core.coef, io, core.device_matrix(), st, lead,
              i0, i1, pos0);
   SMX_HIP_CHECK(hipGetLastError());
 }
@@ -418,12 +412,12 @@ template <typename E, int S>
 void launch_blocks(const char *fn, const IirCore &core, const IirIo &io, double *st, int64_t lead, int64_t first, int64_t nb, hipStream_t stream) {
   constexpr int N = 2 * S, G = N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : 16;
   const int64_t spans = (nb + kSpanBlocks - 1) / kSpanBlocks;
-  if (lead * spans > 2147483647LL) throw Failure(format("%s: too many block spans for one launch", fn));
+  grid_x(fn, "block spans", lead * spans, 64);                // refused before the scratch is taken
   const size_t lds = (size_t)kSpanBlocks * kPitch * sizeof(E);   // 8.25 KB of float32, 16.5 KB of float64
   DeviceScratch ws;
   ws.pool((size_t)lead * (size_t)nb * N * sizeof(double), stream);
   launch_tiles(fn, iir_block_w_kernel<E, S>, lead * spans, 64, lds, stream, core.coef, io, first, nb, spans, ws.as<double>());
-  SMX_LAUNCH((iir_chain_kernel<S>), dim3((unsigned)blocks_of(fn, lead, 64 / G)), dim3(64), 0, stream, core.device_matrix(), st, ws.as<double>(), lead,
+  SMX_LAUNCH((iir_chain_kernel<S>), dim3(grid_x(fn, "workgroups", (lead + 64 / G - 1) / (64 / G), 64)), dim3(64), 0, stream, core.device_matrix(), st, ws.as<double>(), lead,
              nb);
   SMX_HIP_CHECK(hipGetLastError());
   launch_tiles(fn, iir_block_y_kernel<E, S>, lead * spans, 64, lds, stream, core.coef, io, first, nb, spans, (const double *)ws.as<double>());
@@ -465,7 +459,7 @@ void init_records(const char *fn, const IirCore &core, const IirIo &io, int mode
   const int N = 2 * core.S;
   IirZi v{};
   if (zi) std::copy(zi, zi + N, v.v);
-  SMX_LAUNCH(iir_init_kernel, dim3((unsigned)blocks_of(fn, lead * N, 256)), dim3(256), 0, stream, io, v, d_zi_rows, mode, st, lead, N);
+  SMX_LAUNCH(iir_init_kernel, dim3(grid_x(fn, "workgroups", (lead * N + 255) / 256, 256)), dim3(256), 0, stream, io, v, d_zi_rows, mode, st, lead, N);
   SMX_HIP_CHECK(hipGetLastError());
 }
 
@@ -495,7 +489,7 @@ void apply_dev(const IirCore &core, const void *d_x, int elem_bytes, int64_t lea
   init_records(fn, core, io, zi ? ZI_CALL : d_zi_rows ? ZI_ROWS : ZI_ZERO, zi, d_zi_rows, st.as<double>(), lead, stream);
   run_pass(fn, core, io, st.as<double>(), lead, n, 0, stream);
   if (d_zf) {
-    SMX_LAUNCH(iir_state_out_kernel, dim3((unsigned)blocks_of(fn, lead * N, 256)), dim3(256), 0, stream, (const double *)st.as<double>(), d_zf, lead, N);
+    SMX_LAUNCH(iir_state_out_kernel, dim3(grid_x(fn, "workgroups", (lead * N + 255) / 256, 256)), dim3(256), 0, stream, (const double *)st.as<double>(), d_zf, lead, N);
     SMX_HIP_CHECK(hipGetLastError());
   }
 }

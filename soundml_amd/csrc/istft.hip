@@ -955,7 +955,7 @@ void launch_istft(const IstftJob &job) {
   const int64_t adv = quarter ? 13 : 15;      // complete hops per 16-frame tile
   const int64_t fused_tiles = (need + hop * adv - 1) / (hop * adv);
   if (!f64 && job.z_bytes == 8 && (quarter || hop * 2 == fft) && (fft == 512 || fft == 1024 || fft == 2048) && istft_takes_factors(job) &&
-      diag_flag("SMX_ISTFT_UNFUSED") != 1 && job.lead * fused_tiles <= 2147483647LL) {
+      diag_flag("SMX_ISTFT_UNFUSED") != 1 && job.lead * fused_tiles <= clips_per_launch(1, (int)(fft / 2))) {   // (one launch of fft / 2 threads a tile)
     IstftArgs fa{};
     fa.z = job.z;
     fa.lead = job.lead;

@@ -162,21 +162,23 @@ void launch_mel_apply(const MelJob &job) {
   if (!f64_interior) {
     static const bool by_tile = diag_flag("SMX_MEL_APPLY_BY_TILE") == 1;   // diagnostic: all blocks in one workgroup
     if (by_tile) {
-      const int64_t blocks = job.lead * a.frame_tiles;
-      if (blocks > 0x7fffffff) throw Failure("apply: too many frame tiles for one launch");
-      SMX_LAUNCH(mel_apply_mfma_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, job.stream, a);
+      SMX_LAUNCH(mel_apply_mfma_kernel<false>, dim3(grid_x("apply", "frame tiles", job.lead * a.frame_tiles, 256)), dim3(256), 0, job.stream, a);
     } else {
       const int64_t blocks = (job.lead * a.frame_tiles + 3) / 4 * a.mel_blocks;
-      if (blocks > 0x7fffffff) throw Failure("apply: too many frame tiles for one launch");
-      SMX_LAUNCH(mel_apply_mfma_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, job.stream, a);
+      SMX_LAUNCH(mel_apply_mfma_kernel<true>, dim3(grid_x("apply", "frame tiles", blocks, 256)), dim3(256), 0, job.stream, a);
     }
   } else {
-    if (job.lead > 65535) throw Failure("apply: too many leading slices for one launch");
-    dim3 grid((unsigned)((job.frames + 255) / 256), (unsigned)job.lead);
-    if (job.elem_bytes == 8)
-      SMX_LAUNCH(mel_apply_f64_kernel<double>, grid, dim3(256), 0, job.stream, a);
-    else
-      SMX_LAUNCH(mel_apply_f64_kernel<float>, grid, dim3(256), 0, job.stream, a);
+    const unsigned ftiles = grid_x("apply", "frame tiles", (job.frames + 255) / 256, 256);
+    for (int64_t c0 = 0; c0 < job.lead; c0 += kMaxGridYZ) {        // the slices sit on grid.y: 65535 at a time (DESIGN.md "Launch extents")
+      a.lead = std::min(kMaxGridYZ, job.lead - c0);
+      a.s = (const char *)job.s + c0 * a.bins * job.frames * job.elem_bytes;
+      a.out = (char *)job.out + c0 * a.n_mels * job.frames * job.elem_bytes;
+      const dim3 grid(ftiles, (unsigned)a.lead);
+      if (job.elem_bytes == 8)
+        SMX_LAUNCH(mel_apply_f64_kernel<double>, grid, dim3(256), 0, job.stream, a);
+      else
+        SMX_LAUNCH(mel_apply_f64_kernel<float>, grid, dim3(256), 0, job.stream, a);
+    }
   }
   SMX_HIP_CHECK(hipGetLastError());
 }

@@ -392,14 +392,14 @@ void run_invert(const MelInvertJob &job, InvArgs a) {
   }
   // one workgroup per frame, at most kGeneralScratch bytes of s / y / r at a time
   const int64_t per_frame = (2 * (int64_t)a.nbins + a.n_mels + kGatherSlack) * (int64_t)sizeof(T);
-  const int64_t chunk = std::min<int64_t>(std::max<int64_t>(1, kGeneralScratch / per_frame), std::min<int64_t>(a.total, 0x7fffffff));
+  const int64_t chunk = std::min<int64_t>(std::max<int64_t>(1, kGeneralScratch / per_frame), std::min<int64_t>(a.total, clips_per_launch(1, 256)));
   DeviceScratch scratch;
   scratch.pool((size_t)(chunk * per_frame), job.stream);
   a.scratch = scratch.ptr;
   for (int64_t first = 0; first < a.total; first += chunk) {
     a.first = first;
     const int64_t count = std::min(chunk, a.total - first);
-    SMX_LAUNCH(mel_invert_general_kernel<T>, dim3((unsigned)count), dim3(256), 0, job.stream, a);
+    SMX_LAUNCH(mel_invert_general_kernel<T>, dim3(grid_x("invert", "frames", count, 256)), dim3(256), 0, job.stream, a);
     SMX_HIP_CHECK(hipGetLastError());
   }
 }

@@ -398,6 +398,9 @@ void launch_mfcc(const MfccJob &job) {
   // tables: raw DCT-II rows, orthonormal scales (soundml.ml:26-33), lifter weights (soundml.ml:35-42) -- built once per
   // (device, n_mels, n_mfcc, lifter) and kept, so a call uploads nothing and never synchronises its stream
   const double *d_tab = mfcc_tables(n_mels, n_mfcc, job.lifter);
+  // refused, if at all, before the maximum's scratch is taken
+  const unsigned ftiles = grid_x("mfcc", "frame tiles", (job.frames + 255) / 256, 256);
+  const unsigned ftiles4 = grid_x("mfcc", "frame tiles", (job.frames + 63) / 64, 256);
   unsigned long long *d_max = nullptr;
   SMX_HIP_CHECK(smx::pool_malloc_async((void **)&d_max, sizeof(unsigned long long), job.stream));
   SMX_HIP_CHECK(hipMemsetAsync(d_max, 0, sizeof(unsigned long long), job.stream));
@@ -408,33 +411,35 @@ void launch_mfcc(const MfccJob &job) {
   else
     SMX_LAUNCH(mel_max_kernel<float>, dim3(blocks), dim3(256), 0, job.stream, (const float *)job.mel, total, d_max);
   SMX_HIP_CHECK(hipGetLastError());
-  if (job.lead > 65535) throw Failure("mfcc: too many leading slices for one launch");
+  // the maximum above is the whole call's; the slices sit on grid.y and go 65535 at a time (DESIGN.md "Launch extents")
   MfccArgs a{};
-  a.mel = job.mel;
-  a.out = job.out;
   a.dct = d_tab;
   a.post = d_tab + (size_t)n_mfcc * n_mels;
   a.dct_t = a.post + 2 * (size_t)n_mfcc;
   a.max_bits = d_max;
-  a.lead = job.lead;
   a.frames = job.frames;
   a.n_mels = n_mels;
   a.n_mfcc = n_mfcc;
-  dim3 grid((unsigned)((job.frames + 255) / 256), (unsigned)job.lead);
   const int nc = (n_mfcc + 7) / 8 * 8;
-  if (job.elem_bytes == 8) {
-    SMX_LAUNCH(mfcc_kernel<double>, grid, dim3(256), 0, job.stream, a);
-  } else if (n_mfcc <= kFastMfccMaxCoeffs && diag_flag("SMX_MFCC_PLAIN") != 1) {
-    const dim3 grid4((unsigned)((job.frames + 63) / 64), (unsigned)job.lead);
-    auto go = [&](auto kernel) { SMX_LAUNCH(kernel, grid4, dim3(256), 0, job.stream, a, log_table_device()); };
-    if (nc == 8) go(mfcc_fast_kernel<8>);
-    else if (nc == 16) go(mfcc_fast_kernel<16>);
-    else if (nc == 24) go(mfcc_fast_kernel<24>);
-    else go(mfcc_fast_kernel<32>);
-  } else {
-    SMX_LAUNCH(mfcc_kernel<float>, grid, dim3(256), 0, job.stream, a);
+  for (int64_t c0 = 0; c0 < job.lead; c0 += kMaxGridYZ) {
+    a.lead = std::min(kMaxGridYZ, job.lead - c0);
+    a.mel = (const char *)job.mel + c0 * n_mels * job.frames * job.elem_bytes;
+    a.out = (char *)job.out + c0 * n_mfcc * job.frames * job.elem_bytes;
+    const dim3 grid(ftiles, (unsigned)a.lead);
+    if (job.elem_bytes == 8) {
+      SMX_LAUNCH(mfcc_kernel<double>, grid, dim3(256), 0, job.stream, a);
+    } else if (n_mfcc <= kFastMfccMaxCoeffs && diag_flag("SMX_MFCC_PLAIN") != 1) {
+      const dim3 grid4(ftiles4, (unsigned)a.lead);
+      auto go = [&](auto kernel) { SMX_LAUNCH(kernel, grid4, dim3(256), 0, job.stream, a, log_table_device()); };
+      if (nc == 8) go(mfcc_fast_kernel<8>);
+      else if (nc == 16) go(mfcc_fast_kernel<16>);
+      else if (nc == 24) go(mfcc_fast_kernel<24>);
+      else go(mfcc_fast_kernel<32>);
+    } else {
+      SMX_LAUNCH(mfcc_kernel<float>, grid, dim3(256), 0, job.stream, a);
+    }
+    SMX_HIP_CHECK(hipGetLastError());
   }
-  SMX_HIP_CHECK(hipGetLastError());
   SMX_HIP_CHECK(smx::pool_free_async(d_max, job.stream));
 }
 
@@ -472,23 +477,25 @@ __global__ void __launch_bounds__(256) mfcc_to_mel_kernel(MfccArgs a, double ref
 
 void launch_mfcc_to_mel(const MfccToMelJob &job) {
   if (job.lead <= 0 || job.frames <= 0) return;
-  if (job.lead > 65535) throw Failure("mfcc_to_mel: too many leading slices for one launch");
   const double *d_tab = mfcc_tables(job.n_mels, job.n_mfcc, job.lifter);
   MfccArgs a{};
-  a.mel = job.c;
-  a.out = job.out;
   a.dct = d_tab;
   a.post = d_tab + (size_t)job.n_mfcc * job.n_mels;
-  a.lead = job.lead;
   a.frames = job.frames;
   a.n_mels = job.n_mels;
   a.n_mfcc = job.n_mfcc;
-  dim3 grid((unsigned)((job.frames + 255) / 256), (unsigned)job.lead);
-  auto go = [&](auto kernel) { SMX_LAUNCH(kernel, grid, dim3(256), 0, job.stream, a, job.reference); };
+  const unsigned ftiles = grid_x("mfcc_to_mel", "frame tiles", (job.frames + 255) / 256, 256);
   const bool wide = job.elem_bytes == 8;
-  if (job.n_mfcc <= 32) wide ? go(mfcc_to_mel_kernel<double, 32>) : go(mfcc_to_mel_kernel<float, 32>);
-  else wide ? go(mfcc_to_mel_kernel<double, 0>) : go(mfcc_to_mel_kernel<float, 0>);
-  SMX_HIP_CHECK(hipGetLastError());
+  for (int64_t c0 = 0; c0 < job.lead; c0 += kMaxGridYZ) {          // the slices sit on grid.y: 65535 at a time (DESIGN.md "Launch extents")
+    a.lead = std::min(kMaxGridYZ, job.lead - c0);
+    a.mel = (const char *)job.c + c0 * job.n_mfcc * job.frames * job.elem_bytes;
+    a.out = (char *)job.out + c0 * job.n_mels * job.frames * job.elem_bytes;
+    const dim3 grid(ftiles, (unsigned)a.lead);
+    auto go = [&](auto kernel) { SMX_LAUNCH(kernel, grid, dim3(256), 0, job.stream, a, job.reference); };
+    if (job.n_mfcc <= 32) wide ? go(mfcc_to_mel_kernel<double, 32>) : go(mfcc_to_mel_kernel<float, 32>);
+    else wide ? go(mfcc_to_mel_kernel<double, 0>) : go(mfcc_to_mel_kernel<float, 0>);
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 }  // namespace smx

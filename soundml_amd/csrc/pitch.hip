@@ -526,21 +526,21 @@ void launch_pitch(const char *fn, PitchArgs a, const PitchPlan &plan, hipStream_
   if (a.tile_frames) {
     if constexpr (sizeof(T) == 4) {
       a.tiles = (a.frames + a.tile_frames - 1) / a.tile_frames;
-      if (a.lead * a.tiles > 2147483647LL) throw Failure(format("%s: too many frame tiles for one launch", fn));
+      const dim3 grid(grid_x(fn, "frame tiles", a.lead * a.tiles, 256));
       a.nfull = (int)(a.W / a.hop);
       a.rest = (int)(a.W - a.nfull * a.hop);
       a.groups = (a.pmax + kLags) / kLags;
       const size_t lds = (size_t)((a.tile_frames - 1) * a.hop + a.fl + kSlack) * 4 +
                          (size_t)(a.tile_frames + a.nfull) * a.groups * kLags * 8 * (a.rest ? 2 : 1);
-      SMX_LAUNCH(yin_tile_kernel, dim3((unsigned)(a.lead * a.tiles)), dim3(256), lds, stream, a);
+      SMX_LAUNCH(yin_tile_kernel, grid, dim3(256), lds, stream, a);
     }
   } else {
-    if (a.total > 2147483647LL) throw Failure(format("%s: too many frames for one launch", fn));
-    SMX_LAUNCH((yin_general_kernel<T>), dim3((unsigned)a.total), dim3(256), 0, stream, a);
+    SMX_LAUNCH((yin_general_kernel<T>), dim3(grid_x(fn, "frames", a.total, 256)), dim3(256), 0, stream, a);   // a workgroup per frame
   }
   SMX_HIP_CHECK(hipGetLastError());
-  if (troughs) SMX_LAUNCH((pyin_trough_kernel<T>), dim3((unsigned)((a.total + 63) / 64)), dim3(64), 0, stream, a, *troughs);
-  else SMX_LAUNCH((yin_finish_kernel<T>), dim3((unsigned)((a.total + 63) / 64)), dim3(64), 0, stream, a);
+  const dim3 waves(grid_x(fn, "frames", (a.total + 63) / 64, 64));
+  if (troughs) SMX_LAUNCH((pyin_trough_kernel<T>), waves, dim3(64), 0, stream, a, *troughs);
+  else SMX_LAUNCH((yin_finish_kernel<T>), waves, dim3(64), 0, stream, a);
   SMX_HIP_CHECK(hipGetLastError());
 }
 
@@ -566,7 +566,8 @@ void pitch_dev(const char *fn, const PitchPlan &plan, int64_t border, const void
   a.lags = a.pmax + 1;
   if (plan.fl > 2147483647LL / 2 || count > (int64_t)1 << 40) throw Failure(format("%s: frames too long or too many", fn));
   const int64_t per_clip = count * a.lags * 8;
-  const int64_t step = std::max<int64_t>(1, std::min<int64_t>(lead, kScratchBytes / per_clip));
+  // a clip range fits the scratch and one launch of a workgroup per frame (DESIGN.md "Launch extents"); one clip that does not is refused
+  const int64_t step = std::max<int64_t>(1, std::min({lead, kScratchBytes / per_clip, clips_per_launch(count, 256)}));
   init_device_pool();
   DeviceScratch scratch;
   scratch.pool((size_t)(step * per_clip), stream);
@@ -821,7 +822,7 @@ void pyin_dev(const char *fn, const PyinPlan &p, const void *d_x, int elem_bytes
   const int64_t o_bytes = count * (a.lags * 8 + maxr * 12 + 4 + (in_lds ? 0 : maxr * kTroughBytes));
   const int64_t s_bytes = decode ? count * (maxr * 12 + 12) : 0, b_bytes = decode ? pyin_decode_scratch(count, p.n_bins, p.h) : 0;
   const int64_t D = decode ? std::max<int64_t>(1, std::min<int64_t>(lead, kScratchBytes / (s_bytes + b_bytes))) : lead;
-  const int64_t O = std::max<int64_t>(1, std::min<int64_t>(D, (kScratchBytes - (decode ? D * (s_bytes + b_bytes) : 0)) / o_bytes));
+  const int64_t O = std::max<int64_t>(1, std::min({D, (kScratchBytes - (decode ? D * (s_bytes + b_bytes) : 0)) / o_bytes, clips_per_launch(count, 256)}));
   const auto tables = pyin_device_tables(p);
   init_device_pool();
   DeviceScratch scratch, kept;
@@ -849,7 +850,6 @@ void pyin_dev(const char *fn, const PyinPlan &p, const void *d_x, int elem_bytes
     for (int64_t c0 = d0; c0 < d0 + nd; c0 += O) {
       a.lead = std::min(O, d0 + nd - c0);
       a.total = q.total = a.lead * count;
-      if (a.total > 2147483647LL) throw Failure(format("%s: too many frames for one launch", fn));
       a.x = (const char *)d_x + c0 * x_stride * elem_bytes;
       if (elem_bytes == 8) launch_pitch<double>(fn, a, plan, stream, &q);
       else launch_pitch<float>(fn, a, plan, stream, &q);

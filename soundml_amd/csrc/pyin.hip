@@ -292,10 +292,10 @@ int64_t pyin_decode_scratch(int64_t frames, int64_t n_bins, int64_t half_width) 
 void launch_pyin_decode(const PyinDecodeJob &job) {
   if (job.lead == 0 || job.frames == 0) return;
   const int64_t nb = job.n_bins, h = job.half_width, heff = effective_width(nb, h), pitch = pointer_pitch(nb, h);
-  if (job.frames > (int64_t)1 << 40 || job.lead > 2147483647LL) throw Failure(format("%s: too many frames or clips", job.fn));
+  if (job.frames > (int64_t)1 << 40) throw Failure(format("%s: too many frames or clips", job.fn));
   const auto table = decode_table(nb, h);
   const int64_t per_clip = job.frames * pitch + 16;
-  const int64_t step = std::max<int64_t>(1, std::min<int64_t>(job.lead, kScratchBytes / per_clip));
+  const int64_t step = std::max<int64_t>(1, std::min({job.lead, kScratchBytes / per_clip, clips_per_launch(1, 1024)}));   // a workgroup of at most 1024 per clip
   init_device_pool();
   DeviceScratch scratch;
   scratch.pool((size_t)(step * per_clip), job.stream);

@@ -206,8 +206,7 @@ void direct_run(const smx_resample_config &c, const float *d_x, int64_t x_stride
   a.y = d_y; a.y_stride = y_stride; a.out_first = out_first; a.out_count = out_count;
   a.tiles = ceil_div(out_count, c.threads);
   a.l = (int)c.l; a.m = (int)c.m; a.k = (int)c.k; a.taps4 = c.taps4; a.span = c.span; a.chunk = c.chunk;
-  if (a.tiles > 2147483647LL / channels) throw Failure("resample: too many output tiles for one launch");   // channels fold into grid x
-  const unsigned blocks = (unsigned)(a.tiles * channels);
+  const unsigned blocks = grid_x("resample", "output tiles", a.tiles * channels, (int)c.threads);   // channels fold into grid x
   if (c.staged) {
     const size_t lds = (size_t)(c.span - 1 + c.chunk) * sizeof(float);
     SMX_LAUNCH(resample_direct_kernel<true>, dim3(blocks), dim3(c.threads), lds, stream, a);

@@ -525,18 +525,30 @@ void tempogram_dev(const char *fn, const void *d_env, int64_t lead, int64_t fram
   a.env = d_env, a.w = d_w, a.out = d_out, a.wide = d_wide;
   a.lead = lead, a.frames = frames, a.stride = stride;
   a.W = (int)W, a.b = (int)(W / 2), a.norm = norm ? 1 : 0;
-  if (!fast_path_disabled() && W <= kFastWin) {
+  const bool tile = !fast_path_disabled() && W <= kFastWin;
+  size_t lds = 0;
+  int threads = 256;
+  if (tile) {
     a.groups = (int)((W + kLags - 1) / kLags);
     a.pairs = (a.groups + 1) / 2;
     a.ystride = a.groups * kLags + kLags + 2;                              // rows 16-byte aligned, an odd number of 16-byte groups apart
     a.tiles = (frames + kTileFrames - 1) / kTileFrames;
-    const size_t lds = ((size_t)kTileFrames * a.ystride + kTileFrames) * sizeof(double);
-    const int threads = ((a.pairs * kTileFrames + 63) / 64) * 64;
-    launch_tiles(fn, tempogram_tile_kernel<T>, lead * a.tiles, threads, lds, stream, a);
-  } else {
-    if (lead * frames > 2147483647LL) throw Failure(format("%s: too many frames for one launch", fn));
-    SMX_LAUNCH((tempogram_general_kernel<T>), dim3((unsigned)(lead * frames)), dim3(256), 0, stream, a);
-    SMX_HIP_CHECK(hipGetLastError());
+    lds = ((size_t)kTileFrames * a.ystride + kTileFrames) * sizeof(double);
+    threads = ((a.pairs * kTileFrames + 63) / 64) * 64;
+  }
+  // clip range by clip range (DESIGN.md "Launch extents"): a tile kernel's workgroup per tile, the general one's per frame
+  const int64_t per_clip = tile ? a.tiles : frames, per_launch = std::max<int64_t>(1, clips_per_launch(per_clip, threads));
+  for (int64_t c0 = 0; c0 < lead; c0 += per_launch) {
+    a.lead = std::min(per_launch, lead - c0);
+    a.env = reinterpret_cast<const T *>(d_env) + c0 * stride;
+    a.out = d_out ? reinterpret_cast<T *>(d_out) + c0 * W * frames : nullptr;
+    a.wide = d_wide ? d_wide + c0 * frames * W : nullptr;
+    if (tile) {
+      launch_tiles(fn, tempogram_tile_kernel<T>, a.lead * a.tiles, threads, lds, stream, a);
+    } else {
+      SMX_LAUNCH((tempogram_general_kernel<T>), dim3(grid_x(fn, "frames", a.lead * frames, 256)), dim3(256), 0, stream, a);
+      SMX_HIP_CHECK(hipGetLastError());
+    }
   }
 }
 
@@ -564,7 +576,7 @@ void tempo_dev(const char *fn, const TempoPlan &t, int elem_bytes, const void *d
   if (!d_out || (!d_env && frames)) throw Failure(format("%s: null device pointer", fn));
   const auto window = window_table(SMX_WINDOW_HANN, 0.0, t.W), prior = prior_table(t);
   const int64_t per_clip = std::max<int64_t>(1, frames * t.W * 8);
-  const int64_t step = std::max<int64_t>(1, std::min<int64_t>(lead, kScratchBytes / per_clip));
+  const int64_t step = std::max<int64_t>(1, std::min({lead, kScratchBytes / per_clip, clips_per_launch(1, 256)}));   // tempo_kernel: a workgroup per clip
   init_device_pool();
   DeviceScratch scratch;
   scratch.pool((size_t)(step * per_clip), stream);
@@ -581,8 +593,8 @@ void tempo_dev(const char *fn, const TempoPlan &t, int elem_bytes, const void *d
     a.frames = frames;
     a.W = (int)t.W;
     a.want_lag = want_lag ? 1 : 0;
-    if (elem_bytes == 8) SMX_LAUNCH((tempo_kernel<double>), dim3((unsigned)nc), dim3(256), 0, stream, a);
-    else SMX_LAUNCH((tempo_kernel<float>), dim3((unsigned)nc), dim3(256), 0, stream, a);
+    if (elem_bytes == 8) SMX_LAUNCH((tempo_kernel<double>), dim3(grid_x(fn, "clips", nc, 256)), dim3(256), 0, stream, a);
+    else SMX_LAUNCH((tempo_kernel<float>), dim3(grid_x(fn, "clips", nc, 256)), dim3(256), 0, stream, a);
     SMX_HIP_CHECK(hipGetLastError());
   }
 }
@@ -612,7 +624,7 @@ void beat_dev(const char *fn, const BeatPlan &b, int elem_bytes, const void *d_e
   check_beat_frames(fn, frames);
   if (lead == 0) return;
   if (!d_tempo || (frames && (!d_env || !d_beats))) throw Failure(format("%s: null device pointer", fn));
-  if (lead > 2147483647LL) throw Failure(format("%s: too many clips for one launch", fn));
+  grid_x(fn, "clips", lead, 64);                   // beat_kernel: a wave per clip; refused before any scratch is taken
   const int64_t pmin = b.has_bpm ? b.period : 1, pmax = b.has_bpm ? b.period : std::max<int64_t>(1, b.tempo.W - 1);
   const auto tables = beat_table(pmin, pmax, b.tightness);
   std::shared_ptr<void> prior;

@@ -477,25 +477,30 @@ void cost_dev(const char *fn, const Plan &p, int elem_bytes, const void *d_x, in
   CostArgs a = cost_args(p, d_x, xs, d_y, ys);
   a.out = d_out;
   if (fast_path_disabled()) {
-    const int64_t blocks = (p.n * p.m + 255) / 256;
-    if (blocks > 2147483647LL) throw Failure(format("%s: too many cells for one launch", fn));
-    for (int64_t p0 = 0; p0 < pairs; p0 += 65535) {                        // the grid's second axis holds 65535 pairs
-      const int64_t np = std::min<int64_t>(65535, pairs - p0);
+    const unsigned blocks = grid_x(fn, "cells", (p.n * p.m + 255) / 256, 256);
+    for (int64_t p0 = 0; p0 < pairs; p0 += kMaxGridYZ) {                   // the grid's second axis holds 65535 pairs
+      const int64_t np = std::min<int64_t>(kMaxGridYZ, pairs - p0);
       CostArgs b = a;
       b.x = (const char *)d_x + p0 * p.d * xs * elem_bytes, b.y = (const char *)d_y + p0 * p.d * ys * elem_bytes;
       b.out = (char *)d_out + p0 * p.n * p.m * elem_bytes;
-      if (elem_bytes == 8) SMX_LAUNCH((cost_general_kernel<double>), dim3((unsigned)blocks, (unsigned)np), dim3(256), 0, stream, b);
-      else SMX_LAUNCH((cost_general_kernel<float>), dim3((unsigned)blocks, (unsigned)np), dim3(256), 0, stream, b);
+      if (elem_bytes == 8) SMX_LAUNCH((cost_general_kernel<double>), dim3(blocks, (unsigned)np), dim3(256), 0, stream, b);
+      else SMX_LAUNCH((cost_general_kernel<float>), dim3(blocks, (unsigned)np), dim3(256), 0, stream, b);
       SMX_HIP_CHECK(hipGetLastError());
     }
     return;
   }
   a.bi = (p.n + kBlock - 1) / kBlock, a.bj = (p.m + kBlock - 1) / kBlock;
-  if (a.bi * a.bj > 2147483647LL / pairs) throw Failure(format("%s: too many cells for one launch", fn));
-  const int64_t blocks = pairs * a.bi * a.bj;
-  if (elem_bytes == 8) SMX_LAUNCH((cost_kernel<double, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-  else SMX_LAUNCH((cost_kernel<float, false>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-  SMX_HIP_CHECK(hipGetLastError());
+  if (a.bi > kMaxGridBlocks / a.bj) throw Failure(format("%s: too many cells for one launch", fn));   // one pair's blocks, before the product
+  const int64_t per_launch = std::max<int64_t>(1, clips_per_launch(a.bi * a.bj, 256));   // pair range by pair range (DESIGN.md "Launch extents")
+  for (int64_t p0 = 0; p0 < pairs; p0 += per_launch) {
+    const int64_t np = std::min(per_launch, pairs - p0);
+    a.x = (const char *)d_x + p0 * p.d * xs * elem_bytes, a.y = (const char *)d_y + p0 * p.d * ys * elem_bytes;
+    a.out = (char *)d_out + p0 * p.n * p.m * elem_bytes;
+    const unsigned blocks = grid_x(fn, "cells", np * a.bi * a.bj, 256);
+    if (elem_bytes == 8) SMX_LAUNCH((cost_kernel<double, false>), dim3(blocks), dim3(256), 0, stream, a);
+    else SMX_LAUNCH((cost_kernel<float, false>), dim3(blocks), dim3(256), 0, stream, a);
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 // The route table: float32 pairs of at least kTileMinCells cells take the tile kernel, everything else the general one.  Measured
@@ -524,7 +529,11 @@ void dtw_dev(const char *fn, const Plan &p, int elem_bytes, const void *d_x, int
     slots = std::max<int64_t>(1, std::min<int64_t>(maxdiag, room / (kTileScratch * 8)));   // a long diagonal goes in several launches
   }
   const int64_t per_pair = steps_bytes + rev_bytes + edge_bytes + slots * kTileScratch * 8;
-  const int64_t step = std::max<int64_t>(1, std::min<int64_t>(pairs, kScratchBytes / per_pair));
+  // a pair range fits the scratch AND every launch of its route (DESIGN.md "Launch extents"): the end kernel's wave per pair, the
+  // general kernel's 1024 threads per pair, or a diagonal's cost blocks of 256 and tile waves
+  constexpr int per_tile = (kTileRows / kBlock) * (kTileCols / kBlock);
+  const int64_t fit = tiles ? std::min(clips_per_launch(slots * per_tile, 256), clips_per_launch(slots, 64)) : clips_per_launch(1, 1024);
+  const int64_t step = std::max<int64_t>(1, std::min({pairs, kScratchBytes / per_pair, fit, clips_per_launch(1, 64)}));
   init_device_pool();
   DeviceScratch scratch;
   scratch.pool((size_t)(step * per_pair), stream);
@@ -548,9 +557,7 @@ void dtw_dev(const char *fn, const Plan &p, int elem_bytes, const void *d_x, int
           CostArgs c = cost_args(p, x, xs, y, ys);
           c.scratch = costs;
           c.g = (int)g, c.tr_lo = (int)tr_lo, c.q0 = (int)q0, c.nq = (int)nq, c.slots = (int)slots;
-          constexpr int per_tile = (kTileRows / kBlock) * (kTileCols / kBlock);
-          if (np * nq > 2147483647LL / per_tile) throw Failure(format("%s: too many tiles for one launch", fn));
-          SMX_LAUNCH((cost_kernel<float, true>), dim3((unsigned)(np * nq * per_tile)), dim3(256), 0, stream, c);
+          SMX_LAUNCH((cost_kernel<float, true>), dim3(grid_x(fn, "tiles", np * nq * per_tile, 256)), dim3(256), 0, stream, c);
           SMX_HIP_CHECK(hipGetLastError());
           TileArgs t{};
           t.cost = costs, t.hrow = hrow, t.vcol = vcol, t.D = D, t.steps = steps;
@@ -558,25 +565,26 @@ void dtw_dev(const char *fn, const Plan &p, int elem_bytes, const void *d_x, int
           t.tile_rows = (int)tile_rows, t.tile_cols = (int)tile_cols, t.g = (int)g, t.tr_lo = (int)tr_lo, t.q0 = (int)q0, t.nq = (int)nq, t.slots = (int)slots;
           t.subseq = p.subseq ? 1 : 0;
           t.w = p.w;
-          if (store) SMX_LAUNCH((dtw_tile_kernel<true>), dim3((unsigned)(np * nq)), dim3(64), 0, stream, t);
-          else SMX_LAUNCH((dtw_tile_kernel<false>), dim3((unsigned)(np * nq)), dim3(64), 0, stream, t);
+          const unsigned waves = grid_x(fn, "tiles", np * nq, 64);
+          if (store) SMX_LAUNCH((dtw_tile_kernel<true>), dim3(waves), dim3(64), 0, stream, t);
+          else SMX_LAUNCH((dtw_tile_kernel<false>), dim3(waves), dim3(64), 0, stream, t);
           SMX_HIP_CHECK(hipGetLastError());
         }
       }
       e.lastrow = hrow + (tile_rows - 1) * m, e.lr_stride = tile_rows * m;
     } else {
-      if (np > 2147483647LL) throw Failure(format("%s: too many pairs for one launch", fn));
+      const dim3 grid(grid_x(fn, "pairs", np, 1024));
       GeneralArgs a{};
       a.x = x, a.y = y, a.diags = wide, a.lastrow = wide + step * 3 * n, a.D = D, a.steps = steps;
       a.d = p.d, a.n = n, a.m = m, a.xs = xs, a.ys = ys;
       a.metric = p.metric, a.subseq = p.subseq ? 1 : 0;
       a.w = p.w;
       if (elem_bytes == 8) {
-        if (store) SMX_LAUNCH((dtw_general_kernel<double, true>), dim3((unsigned)np), dim3(1024), 0, stream, a);
-        else SMX_LAUNCH((dtw_general_kernel<double, false>), dim3((unsigned)np), dim3(1024), 0, stream, a);
+        if (store) SMX_LAUNCH((dtw_general_kernel<double, true>), grid, dim3(1024), 0, stream, a);
+        else SMX_LAUNCH((dtw_general_kernel<double, false>), grid, dim3(1024), 0, stream, a);
       } else {
-        if (store) SMX_LAUNCH((dtw_general_kernel<float, true>), dim3((unsigned)np), dim3(1024), 0, stream, a);
-        else SMX_LAUNCH((dtw_general_kernel<float, false>), dim3((unsigned)np), dim3(1024), 0, stream, a);
+        if (store) SMX_LAUNCH((dtw_general_kernel<float, true>), grid, dim3(1024), 0, stream, a);
+        else SMX_LAUNCH((dtw_general_kernel<float, false>), grid, dim3(1024), 0, stream, a);
       }
       SMX_HIP_CHECK(hipGetLastError());
       e.lastrow = a.lastrow, e.lr_stride = m;
@@ -585,8 +593,9 @@ void dtw_dev(const char *fn, const Plan &p, int elem_bytes, const void *d_x, int
     e.path = store ? (char *)d_path + p0 * 2 * L * elem_bytes : nullptr;
     e.dist = d_dist ? (char *)d_dist + p0 * elem_bytes : nullptr;
     e.n = n, e.m = m, e.subseq = p.subseq ? 1 : 0;
-    if (elem_bytes == 8) SMX_LAUNCH((dtw_end_kernel<double>), dim3((unsigned)np), dim3(64), 0, stream, e);
-    else SMX_LAUNCH((dtw_end_kernel<float>), dim3((unsigned)np), dim3(64), 0, stream, e);
+    const dim3 ends(grid_x(fn, "pairs", np, 64));
+    if (elem_bytes == 8) SMX_LAUNCH((dtw_end_kernel<double>), ends, dim3(64), 0, stream, e);
+    else SMX_LAUNCH((dtw_end_kernel<float>), ends, dim3(64), 0, stream, e);
     SMX_HIP_CHECK(hipGetLastError());
   }
 }

@@ -83,13 +83,33 @@ extern std::atomic<unsigned long long> g_kernel_launches;
     hipLaunchKernelGGL(__VA_ARGS__);                                          \
   } while (0)
 
+// ---- launch extents (DESIGN.md "Launch extents") -------------------------------------------------------------------
+// The dispatch packet holds a grid axis in WORK-ITEMS in 32 bits, so one launch is legal only while blocks x threads <= 2^32 - 1
+// (and blocks <= 2^31 - 1, the runtime's own bound on a dim3 axis).  These two functions are the library's only statement of that.
+constexpr int64_t kMaxGridBlocks = 2147483647LL;
+constexpr int64_t kMaxGridItems = 4294967295LL;
+constexpr int64_t kMaxGridYZ = 65535;   // slices on grid.y / grid.z of one launch
+
+// the most clips one launch holds when a clip takes `tiles_per_clip` workgroups of `threads`; 0: a single clip does not fit
+inline int64_t clips_per_launch(int64_t tiles_per_clip, int threads) {
+  if (tiles_per_clip < 1 || threads < 1) return 0;
+  return std::min(kMaxGridBlocks, kMaxGridItems / threads) / tiles_per_clip;
+}
+
+// grid.x of a launch of `blocks` workgroups of `threads`, or the worded refusal "<fn>: too many <what> for one launch"
+inline unsigned grid_x(const char *fn, const char *what, int64_t blocks, int threads) {
+  if (blocks > kMaxGridBlocks || blocks * (int64_t)threads > kMaxGridItems)
+    throw Failure(format("%s: too many %s for one launch", fn, what));
+  return (unsigned)blocks;
+}
+
 // One launch of `blocks` workgroups of a frame-tile kernel with `lds` bytes of dynamic LDS (past the 64 KB a kernel gets unasked);
 // `what` names the entry point in the error ("stft", "invert")
 template <typename K, typename... Args>
 void launch_tiles(const char *what, K kernel, int64_t blocks, int threads, size_t lds, hipStream_t stream, const Args &...args) {
-  if (blocks > 2147483647LL) throw Failure(format("%s: too many frame tiles for one launch", what));
+  const unsigned grid = grid_x(what, "frame tiles", blocks, threads);
   SMX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SMX_LAUNCH(kernel, dim3((unsigned)blocks), dim3(threads), lds, stream, args...);
+  SMX_LAUNCH(kernel, dim3(grid), dim3(threads), lds, stream, args...);
   SMX_HIP_CHECK(hipGetLastError());
 }
 

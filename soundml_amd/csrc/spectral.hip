@@ -168,12 +168,19 @@ __global__ void __launch_bounds__(64 * Q * tiles_of<Q>) spectral_kernel(Spectral
 }
 
 template <typename T, int FEATURE, int Q>
-void launch_feature(const SpectralArgs &a, hipStream_t stream) {
-  constexpr int kTiles = tiles_of<Q>;
-  const int64_t blocks = a.lead * ((a.ftiles + kTiles - 1) / kTiles);
-  if (blocks > 2147483647LL) throw Failure("spectral: too many frame tiles for one launch");
-  SMX_LAUNCH((spectral_kernel<T, FEATURE, Q>), dim3((unsigned)blocks), dim3(64 * Q * kTiles), 0, stream, a);
-  SMX_HIP_CHECK(hipGetLastError());
+void launch_feature(const SpectralArgs &whole, hipStream_t stream) {
+  constexpr int kTiles = tiles_of<Q>, kThreads = 64 * Q * kTiles;
+  const int64_t groups = (whole.ftiles + kTiles - 1) / kTiles;
+  const int64_t per_launch = std::max<int64_t>(1, clips_per_launch(groups, kThreads));   // clip range by clip range (DESIGN.md "Launch extents")
+  for (int64_t c0 = 0; c0 < whole.lead; c0 += per_launch) {
+    SpectralArgs a = whole;
+    a.lead = std::min(per_launch, whole.lead - c0);
+    a.s = reinterpret_cast<const T *>(whole.s) + c0 * whole.bins * whole.frames;
+    a.out = reinterpret_cast<T *>(whole.out) + c0 * whole.frames;
+    if (whole.centroid) a.centroid = reinterpret_cast<const T *>(whole.centroid) + c0 * whole.frames;
+    SMX_LAUNCH((spectral_kernel<T, FEATURE, Q>), dim3(grid_x("spectral", "frame tiles", a.lead * groups, kThreads)), dim3(kThreads), 0, stream, a);
+    SMX_HIP_CHECK(hipGetLastError());
+  }
 }
 
 template <typename T>
@@ -315,17 +322,17 @@ void launch_chroma(const ChromaJob &job) {
   a.norm_p = job.norm_p;
   a.inv_p = job.norm == SMX_CHROMA_NORM_P ? 1.0 / job.norm_p : 1.0;
   a.tiny = job.elem_bytes == 8 ? DBL_MIN : (double)FLT_MIN;   // chroma.ml:42-55 smallest_normal
-  const int64_t blocks = a.lead * a.ftiles;
   const int64_t chunks = (n_chroma + kChromaChunk - 1) / kChromaChunk;
-  if (blocks > 2147483647LL || chunks > 65535) throw Failure("chroma: too many tiles for one launch");
+  if (chunks > kMaxGridYZ) throw Failure("chroma: too many tiles for one launch");
+  const unsigned blocks = grid_x("chroma", "tiles", a.lead * a.ftiles, 256);
   SMX_HIP_CHECK(smx::pool_malloc_async((void **)&a.raw, (size_t)job.lead * (size_t)n_chroma * (size_t)job.frames * sizeof(double),
                                job.stream));
   if (job.elem_bytes == 8) {
-    SMX_LAUNCH(chroma_project_kernel<double>, dim3((unsigned)blocks, (unsigned)chunks), dim3(256), 0, job.stream, a);
-    SMX_LAUNCH(chroma_normalise_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, job.stream, a);
+    SMX_LAUNCH(chroma_project_kernel<double>, dim3(blocks, (unsigned)chunks), dim3(256), 0, job.stream, a);
+    SMX_LAUNCH(chroma_normalise_kernel<double>, dim3(blocks), dim3(256), 0, job.stream, a);
   } else {
-    SMX_LAUNCH(chroma_project_kernel<float>, dim3((unsigned)blocks, (unsigned)chunks), dim3(256), 0, job.stream, a);
-    SMX_LAUNCH(chroma_normalise_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, job.stream, a);
+    SMX_LAUNCH(chroma_project_kernel<float>, dim3(blocks, (unsigned)chunks), dim3(256), 0, job.stream, a);
+    SMX_LAUNCH(chroma_normalise_kernel<float>, dim3(blocks), dim3(256), 0, job.stream, a);
   }
   SMX_HIP_CHECK(hipGetLastError());
   SMX_HIP_CHECK(smx::pool_free_async(a.raw, job.stream));

@@ -394,8 +394,7 @@ void launch_interior(const StftJob &job, const FastTarget &tg, const float *x, i
   const bool p64 = c.fft_size == k64N;   // fft 4096: a frame in a whole wave, 8-frame tiles (stft_fast_p64.hpp; power output only)
   const int64_t ft = p64 ? k64FT : lanes == 16 ? PL<16>::FT : lanes == 8 ? PL<8>::FT : lanes == 4 ? PL<4>::FT : kFT, bins = c.fft_size / 2 + 1;
   const int64_t tiles = (count + ft - 1) / ft;
-  if (tiles > 0x7fffffff) throw Failure("stft: too many frame tiles for one launch");
-  a.tiles_per_clip = (int)tiles;
+  a.tiles_per_clip = (int)grid_x("stft", "frame tiles", tiles, 1);   // (an int field: the launch itself is one workgroup per CU)
   // persistent workgroups: one per CU (160 KB of LDS each), every one walks a contiguous range of the
   // flat (clip, tile) sequence, so the table fill / first-load latency / final flush are paid once
   a.total_tiles = job.lead * tiles;

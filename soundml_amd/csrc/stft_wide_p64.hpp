@@ -473,7 +473,7 @@ __global__ void __launch_bounds__(512) stft2048_power_wide_kernel(Args A) {
 
 // what the kernel takes of the fft-2048 / float32-audio / power requests: row offsets within 32 bits, tile counts within 31
 inline bool serves(const StftJob &job, const GenericArgs &g) {
-  if (job.mode == OUT_COMPLEX || g.bins * g.out_stride * 4 >= (int64_t(1) << 32) || (g.count + kFT - 1) / kFT > 0x7fffffff) return false;
+  if (job.mode == OUT_COMPLEX || g.bins * g.out_stride * 4 >= (int64_t(1) << 32) || (g.count + kFT - 1) / kFT > kMaxGridBlocks) return false;
   return env_flag("SMX_WIDE_PIPELINE") != 0;   // "0": the one-tile-per-workgroup kernel (A/B timing, bit-identical)
 }
 
