@@ -1382,6 +1382,84 @@ int smx_iir_kernel_step_f32(smx_iir_kernel *k, const float *x, int64_t m, float 
 int smx_iir_kernel_step_f64(smx_iir_kernel *k, const double *x, int64_t m, double *out);
 int smx_iir_kernel_step_card_f32(smx_iir_kernel *k, void *stream, const float *d_x, int64_t m, int64_t x_stride, float *d_out);
 
+/* ---- Loudness: programme loudness and true peak (ITU-R BS.1770-4; the meter's windows and compliance signals: EBU Tech 3341;
+ * the reference has no such module) ------------------------------------------------------------------------------------------
+ * Audio is [clips; channels; n], time fastest, 1 <= channels <= smx_loudness_max_channels() = 32.  DESIGN.md 4.8l states every
+ * order once; every face, both kernels and every chunking of the meter share it bit for bit.
+ *
+ *   smx_loudness_k_weighting   BS.1770-4 Annex 1: the shelf and the RLB high-pass as two second-order sections [2; 6] (rows
+ *                     b0 b1 b2 1 a1 a2) designed from their analogue prototypes by the bilinear transform; at 48000 Hz the
+ *                     recommendation's printed table.  rate < smx_loudness_min_rate() = 8000 is refused.
+ *   the grid          BS.1770-4 Annex 1 gating blocks: step = smx_loudness_step(rate) = (rate + 5) / 10 samples (100 ms), a
+ *                     block is 4 steps (400 ms, 75 % overlap), nb = smx_loudness_blocks(rate, n) whole blocks, a trailing partial
+ *                     block is dropped.  Short-term windows (EBU Tech 3341: 3 s) are 30 steps at the same hop.
+ *   smx_loudness_block_energy_*  z [clips; channels; nb] float64: the mean square of each channel's K-weighted signal over each
+ *                     block (BS.1770-4 eq. 1).  The cascade runs in float64 from a zero state by Iir's stated order (4.8k); the
+ *                     weighted signal is never rounded and never stored.
+ *   smx_loudness_momentary_*   -0.691 + 10 log10(sum_c G_c z[c, j]) per block (BS.1770-4 eq. 2; EBU Tech 3341 momentary), or with
+ *                     short_term != 0 over the 30-step windows: [clips; nb] or [clips; max(0, nb - 26)].  weights: host
+ *                     [channels] or NULL (1.0 each).  A zero-energy block gives -inf.
+ *   smx_loudness_integrated_*  BS.1770-4 eqs. 3-7: the absolute gate e > smx_loudness_absolute_gate() = 10^((-70 + 0.691) / 10),
+ *                     the relative gate e > 0.1 mean(e through the absolute gate), -0.691 + 10 log10(mean of the blocks through
+ *                     both); no such block: -inf.  mask: NULL, or [clips; nb] bytes: bit 0 through the absolute gate, bit 1 both.
+ *   smx_loudness_true_peak_*   BS.1770-4 Annex 2 with the taps of smx_loudness_true_peak_taps (49-tap Kaiser sinc, 4x):
+ *                     max_i,p |sum_j h[p + 4 j] x[i - j]| per row, zeros outside the signal, a linear amplitude.
+ *   smx_loudness_normalize_*   one gain per clip, 10^((target - integrated) / 20), lowered until gain * max_c true_peak <=
+ *                     ceiling when has_ceiling; a clip at -inf keeps gain 1.  Float64 on the device, one rounding.
+ *   smx_loudness_meter_*  Loudness.Meter (EBU Tech 3341's live meter): per channel Iir's record, the open piece's partial sum and
+ *                     the step energies so far stay on the device; the position is a host integer.  A step takes
+ *                     [clips; channels; len] and returns the momentary loudness [clips; k] of the k blocks that completed,
+ *                     k = max(0, (position + len) / step - 3) - max(0, position / step - 3).  read: what 0 = integrated
+ *                     [clips], 1 = short-term [clips; max(0, blocks - 26)] of everything fed so far.
+ *
+ * The device-resident forms end in `_card_f32` and take the stream directly after the first argument (tables and laws of their
+ * own: tests/test_gpu_placement_loudness.py, tests/test_gpu_streams_loudness.py).  Rows of d_x (one per clip and channel) lie
+ * x_stride >= n apart, results are dense.  Everything is enqueued on `stream`; nothing synchronises it. */
+typedef struct smx_loudness_meter smx_loudness_meter;
+int64_t smx_loudness_min_rate(void);
+int64_t smx_loudness_max_channels(void);
+int64_t smx_loudness_step(int64_t rate);
+int64_t smx_loudness_blocks(int64_t rate, int64_t n);
+double smx_loudness_absolute_gate(void);
+int smx_loudness_k_weighting(int64_t rate, double *sos /* [2; 6] */);
+int smx_loudness_true_peak_taps(double *h /* [49] */);
+int smx_loudness_block_energy_f32(const float *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, double *z);
+int smx_loudness_block_energy_f64(const double *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, double *z);
+int smx_loudness_block_energy_card_f32(const float *d_x, void *stream, int64_t clips, int64_t channels, int64_t n, int64_t x_stride,
+                                       int64_t rate, double *d_z);
+int smx_loudness_momentary_f32(const float *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, const double *weights,
+                               int short_term, float *out);
+int smx_loudness_momentary_f64(const double *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, const double *weights,
+                               int short_term, double *out);
+int smx_loudness_momentary_card_f32(const float *d_x, void *stream, int64_t clips, int64_t channels, int64_t n, int64_t x_stride,
+                                    int64_t rate, const double *weights, int short_term, float *d_out);
+int smx_loudness_integrated_f32(const float *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, const double *weights,
+                                float *out, unsigned char *mask);
+int smx_loudness_integrated_f64(const double *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, const double *weights,
+                                double *out, unsigned char *mask);
+int smx_loudness_integrated_card_f32(const float *d_x, void *stream, int64_t clips, int64_t channels, int64_t n, int64_t x_stride,
+                                     int64_t rate, const double *weights, float *d_out, unsigned char *d_mask);
+int smx_loudness_true_peak_f32(const float *x, int64_t rows, int64_t n, float *out);
+int smx_loudness_true_peak_f64(const double *x, int64_t rows, int64_t n, double *out);
+int smx_loudness_true_peak_card_f32(const float *d_x, void *stream, int64_t rows, int64_t n, int64_t x_stride, float *d_out);
+int smx_loudness_normalize_f32(const float *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, double target,
+                               int has_ceiling, double ceiling, const double *weights, float *out);
+int smx_loudness_normalize_f64(const double *x, int64_t clips, int64_t channels, int64_t n, int64_t rate, double target,
+                               int has_ceiling, double ceiling, const double *weights, double *out);
+int smx_loudness_normalize_card_f32(const float *d_x, void *stream, int64_t clips, int64_t channels, int64_t n, int64_t x_stride,
+                                    int64_t rate, double target, int has_ceiling, double ceiling, const double *weights, float *d_out);
+int smx_loudness_meter_prepare(int64_t rate, int64_t clips, int64_t channels, const double *weights, smx_loudness_meter **out);
+void smx_loudness_meter_destroy(smx_loudness_meter *m);
+int smx_loudness_meter_reset(smx_loudness_meter *m);
+int smx_loudness_meter_flush(smx_loudness_meter *m);
+int64_t smx_loudness_meter_position(const smx_loudness_meter *m);   /* samples per channel since reset */
+int smx_loudness_meter_step_f32(smx_loudness_meter *m, const float *x, int64_t len, float *out);
+int smx_loudness_meter_step_f64(smx_loudness_meter *m, const double *x, int64_t len, double *out);
+int smx_loudness_meter_step_card_f32(smx_loudness_meter *m, void *stream, const float *d_x, int64_t len, int64_t x_stride, float *d_out);
+int smx_loudness_meter_read_f32(smx_loudness_meter *m, int what, float *out);
+int smx_loudness_meter_read_f64(smx_loudness_meter *m, int what, double *out);
+int smx_loudness_meter_read_card_f32(smx_loudness_meter *m, void *stream, int what, float *d_out);
+
 #ifdef __cplusplus
 }
 #endif

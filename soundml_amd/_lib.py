@@ -430,6 +430,39 @@ SIGNATURES = {
     "smx_iir_kernel_step_f32": (cint, [vp, vp, i64, vp]),
     "smx_iir_kernel_step_f64": (cint, [vp, vp, i64, vp]),
     "smx_iir_kernel_step_card_f32": (cint, [vp, vp, vp, i64, i64, vp]),
+    "smx_loudness_min_rate": (i64, []),
+    "smx_loudness_max_channels": (i64, []),
+    "smx_loudness_step": (i64, [i64]),
+    "smx_loudness_blocks": (i64, [i64, i64]),
+    "smx_loudness_absolute_gate": (f64, []),
+    "smx_loudness_k_weighting": (cint, [i64, vp]),
+    "smx_loudness_true_peak_taps": (cint, [vp]),
+    "smx_loudness_block_energy_f32": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_loudness_block_energy_f64": (cint, [vp, i64, i64, i64, i64, vp]),
+    "smx_loudness_block_energy_card_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, vp]),
+    "smx_loudness_momentary_f32": (cint, [vp, i64, i64, i64, i64, vp, cint, vp]),
+    "smx_loudness_momentary_f64": (cint, [vp, i64, i64, i64, i64, vp, cint, vp]),
+    "smx_loudness_momentary_card_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, vp, cint, vp]),
+    "smx_loudness_integrated_f32": (cint, [vp, i64, i64, i64, i64, vp, vp, vp]),
+    "smx_loudness_integrated_f64": (cint, [vp, i64, i64, i64, i64, vp, vp, vp]),
+    "smx_loudness_integrated_card_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp]),
+    "smx_loudness_true_peak_f32": (cint, [vp, i64, i64, vp]),
+    "smx_loudness_true_peak_f64": (cint, [vp, i64, i64, vp]),
+    "smx_loudness_true_peak_card_f32": (cint, [vp, vp, i64, i64, i64, vp]),
+    "smx_loudness_normalize_f32": (cint, [vp, i64, i64, i64, i64, f64, cint, f64, vp, vp]),
+    "smx_loudness_normalize_f64": (cint, [vp, i64, i64, i64, i64, f64, cint, f64, vp, vp]),
+    "smx_loudness_normalize_card_f32": (cint, [vp, vp, i64, i64, i64, i64, i64, f64, cint, f64, vp, vp]),
+    "smx_loudness_meter_prepare": (cint, [i64, i64, i64, vp, C.POINTER(vp)]),
+    "smx_loudness_meter_destroy": (None, [vp]),
+    "smx_loudness_meter_reset": (cint, [vp]),
+    "smx_loudness_meter_flush": (cint, [vp]),
+    "smx_loudness_meter_position": (i64, [vp]),
+    "smx_loudness_meter_step_f32": (cint, [vp, vp, i64, vp]),
+    "smx_loudness_meter_step_f64": (cint, [vp, vp, i64, vp]),
+    "smx_loudness_meter_step_card_f32": (cint, [vp, vp, vp, i64, i64, vp]),
+    "smx_loudness_meter_read_f32": (cint, [vp, cint, vp]),
+    "smx_loudness_meter_read_f64": (cint, [vp, cint, vp]),
+    "smx_loudness_meter_read_card_f32": (cint, [vp, vp, cint, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

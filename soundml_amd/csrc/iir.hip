@@ -36,9 +36,9 @@
 namespace smx {
 namespace {
 
-constexpr int kBlock = 256;                  // B
-constexpr int kSpanBlocks = 64;              // blocks per wave: one per lane
-constexpr int kMaxSections = 8;
+constexpr int kBlock = kIirBlock;            // B
+constexpr int kSpanBlocks = kIirSpanBlocks;  // blocks per wave: one per lane
+constexpr int kMaxSections = kIirMaxSections;
 constexpr int kPhase = 32, kLogPhase = 5;    // samples of every block of the span that lie in LDS at a time
 constexpr int kPitch = kPhase + 1;           // LDS row pitch in elements
 constexpr int kAhead = 8;                    // LDS reads a lane issues before it uses the first
@@ -48,9 +48,6 @@ enum { SRC_PLAIN = 0, SRC_EXT = 1, SRC_REV = 2 };
 enum { DST_PLAIN = 0, DST_REV_TRIM = 1 };
 enum { ZI_ZERO = 0, ZI_CALL = 1, ZI_ROWS = 2, ZI_SCALED = 3 };
 
-struct IirCoef {
-  double c[kMaxSections][5];   // b0 b1 b2 a1 a2
-};
 struct IirZi {
   double v[2 * kMaxSections];
 };
@@ -87,16 +84,10 @@ __device__ __forceinline__ void store_dst(const IirIo &io, int64_t c, int64_t i,
   else reinterpret_cast<double *>(io.out)[c * io.out_stride + j] = y;
 }
 
+// (the cascade itself is smx_internal.hpp's iir_cascade: Loudness runs it too)
 template <int S>
 __device__ __forceinline__ double cascade(const IirCoef &k, double u, double (&z)[2 * S]) {
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const double y = k.c[s][0] * u + z[2 * s];
-    z[2 * s] = (k.c[s][1] * u - k.c[s][3] * y) + z[2 * s + 1];
-    z[2 * s + 1] = k.c[s][2] * u - k.c[s][4] * y;
-    u = y;
-  }
-  return u;
+  return iir_cascade<S>(k, u, z);
 }
 
 // load_src with the element type and the mode fixed at compile time and no branch around a load: the extension reads the mirrored
@@ -408,18 +399,27 @@ void launch_general(const char *fn, const IirCore &core, const IirIo &io, double
   SMX_HIP_CHECK(hipGetLastError());
 }
 
+// the zero-state pass and the chain: ws [lead; nb; 2S] leaves with s_b
 template <typename E, int S>
-void launch_blocks(const char *fn, const IirCore &core, const IirIo &io, double *st, int64_t lead, int64_t first, int64_t nb, hipStream_t stream) {
+void launch_block_states(const char *fn, const IirCore &core, const IirIo &io, double *st, int64_t lead, int64_t first, int64_t nb, double *ws,
+                         hipStream_t stream) {
   constexpr int N = 2 * S, G = N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : 16;
   const int64_t spans = (nb + kSpanBlocks - 1) / kSpanBlocks;
-  grid_x(fn, "block spans", lead * spans, 64);                // refused before the scratch is taken
   const size_t lds = (size_t)kSpanBlocks * kPitch * sizeof(E);   // 8.25 KB of float32, 16.5 KB of float64
+  launch_tiles(fn, iir_block_w_kernel<E, S>, lead * spans, 64, lds, stream, core.coef, io, first, nb, spans, ws);
+  SMX_LAUNCH((iir_chain_kernel<S>), dim3(grid_x(fn, "workgroups", (lead + 64 / G - 1) / (64 / G), 64)), dim3(64), 0, stream, core.device_matrix(), st, ws, lead, nb);
+  SMX_HIP_CHECK(hipGetLastError());
+}
+
+template <typename E, int S>
+void launch_blocks(const char *fn, const IirCore &core, const IirIo &io, double *st, int64_t lead, int64_t first, int64_t nb, hipStream_t stream) {
+  constexpr int N = 2 * S;
+  const int64_t spans = (nb + kSpanBlocks - 1) / kSpanBlocks;
+  grid_x(fn, "block spans", lead * spans, 64);                // refused before the scratch is taken
+  const size_t lds = (size_t)kSpanBlocks * kPitch * sizeof(E);
   DeviceScratch ws;
   ws.pool((size_t)lead * (size_t)nb * N * sizeof(double), stream);
-  launch_tiles(fn, iir_block_w_kernel<E, S>, lead * spans, 64, lds, stream, core.coef, io, first, nb, spans, ws.as<double>());
-  SMX_LAUNCH((iir_chain_kernel<S>), dim3(grid_x(fn, "workgroups", (lead + 64 / G - 1) / (64 / G), 64)), dim3(64), 0, stream, core.device_matrix(), st, ws.as<double>(), lead,
-             nb);
-  SMX_HIP_CHECK(hipGetLastError());
+  launch_block_states<E, S>(fn, core, io, st, lead, first, nb, ws.as<double>(), stream);
   launch_tiles(fn, iir_block_y_kernel<E, S>, lead * spans, 64, lds, stream, core.coef, io, first, nb, spans, (const double *)ws.as<double>());
 }
 
@@ -548,7 +548,36 @@ void filtfilt_host(const IirCore &core, const void *x, int elem_bytes, int64_t l
   });
 }
 
+template <int S>
+void block_states(const char *fn, const IirCore &core, const IirIo &io, double *st, int64_t lead, int64_t first, int64_t nb, double *ws, hipStream_t stream) {
+  if (io.x_bytes == 4) launch_block_states<float, S>(fn, core, io, st, lead, first, nb, ws, stream);
+  else launch_block_states<double, S>(fn, core, io, st, lead, first, nb, ws, stream);
+}
+
 }  // namespace
+
+// ---- what smx_internal.hpp offers the modules built on the block route ------------------------------------------------------------
+std::shared_ptr<IirCore> iir_make_core(const double *sos, int64_t sections) { return make_core(sos, sections); }
+const IirCoef &iir_coef(const IirCore &core) { return core.coef; }
+const double *iir_device_matrix(const IirCore &core) { return core.device_matrix(); }
+
+void iir_block_states(const char *fn, const IirCore &core, const void *d_x, int x_bytes, int64_t x_stride, double *st, int64_t lead, int64_t first,
+                      int64_t nb, double *ws, hipStream_t stream) {
+  if (lead == 0 || nb == 0) return;
+  const IirIo io = plain_io(d_x, x_bytes, x_stride, nullptr, x_bytes, 0, first + nb * kBlock);
+  switch (core.S) {
+    case 1: return block_states<1>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 2: return block_states<2>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 3: return block_states<3>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 4: return block_states<4>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 5: return block_states<5>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 6: return block_states<6>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 7: return block_states<7>(fn, core, io, st, lead, first, nb, ws, stream);
+    case 8: return block_states<8>(fn, core, io, st, lead, first, nb, ws, stream);
+    default: throw Failure(format("%s: a cascade of %d sections has no kernel", fn, core.S));
+  }
+}
+
 }  // namespace smx
 
 struct smx_iir {

@@ -694,6 +694,36 @@ void launch_pyin_decode(const PyinDecodeJob &job);
 double pyin_triangle(int64_t k, int64_t h);                              // tri[k] = 1 - |k - h| / (h + 1)
 void pyin_band_scale(int64_t n_bins, int64_t h, double *rs);             // rs[i] = 1 / (the band's sum of tri over the targets in [0, n_bins))
 
+// ---- Iir's cascade and block route for the modules built on them (iir.hip) ------------------------------------
+constexpr int kIirBlock = 256;         // B
+constexpr int kIirSpanBlocks = 64;     // blocks per wave of the block route: one per lane
+constexpr int kIirMaxSections = 8;
+struct IirCoef {
+  double c[kIirMaxSections][5];   // b0 b1 b2 a1 a2
+};
+// one sample through the cascade, every product and every sum rounded on its own (the files that use it are built with
+// -ffp-contract=off)
+template <int S>
+__device__ __forceinline__ double iir_cascade(const IirCoef &k, double u, double (&z)[2 * S]) {
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const double y = k.c[s][0] * u + z[2 * s];
+    z[2 * s] = (k.c[s][1] * u - k.c[s][3] * y) + z[2 * s + 1];
+    z[2 * s + 1] = k.c[s][2] * u - k.c[s][4] * y;
+    u = y;
+  }
+  return u;
+}
+struct IirCore;
+std::shared_ptr<IirCore> iir_make_core(const double *sos, int64_t sections);   // Iir.Config.create's checks and tables
+const IirCoef &iir_coef(const IirCore &core);
+const double *iir_device_matrix(const IirCore &core);   // M [2S; 2S] on the current device, uploaded once
+// The zero-state pass and the chain of the block route over the nb whole blocks that start at sample `first` of `lead` rows of
+// float32 (x_bytes 4) or float64 samples: ws [lead; nb; 2S] holds s_b, the state entering block b, on return; the records
+// st [lead; 6S] enter with s_0 and leave with s_nb as block state and running state and a zero partial.
+void iir_block_states(const char *fn, const IirCore &core, const void *d_x, int x_bytes, int64_t x_stride, double *st, int64_t lead,
+                      int64_t first, int64_t nb, double *ws, hipStream_t stream);
+
 // A host-built table on the current device, built once per key and device and kept (rhythm.hip); the holder keeps it alive
 // through the enqueue
 std::shared_ptr<void> cached_table(const std::string &key, const std::function<std::vector<unsigned char>()> &make);
