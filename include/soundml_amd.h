@@ -1460,6 +1460,71 @@ int smx_loudness_meter_read_f32(smx_loudness_meter *m, int what, float *out);
 int smx_loudness_meter_read_f64(smx_loudness_meter *m, int what, double *out);
 int smx_loudness_meter_read_card_f32(smx_loudness_meter *m, void *stream, int what, float *d_out);
 
+/* ---- Pcen: per-channel energy normalisation (Wang et al. 2017; Lostanlen et al. 2019; librosa.pcen with max_size = 1; the
+ * reference has no such module) ----------------------------------------------------------------------------------------------
+ * S is [rows; frames], non-negative and finite, frames fastest; a row is one (leading index, band).  Float64 inside, every
+ * product, quotient and sum rounded on its own (no fused operation), one rounding to the dtype of the input:
+ *     u[t] = scale * (double)S[t]
+ *     M[t] = a * M[t-1] + s * u[t]          the two products, then the sum; M[-1] = zi[row], or u[0] when zi is NULL
+ *     sm   = exp(-gain * (log(eps) + log1p(M[t] / eps)))
+ *     out  = log1p(u * sm / bias)                                   power == 0
+ *          = exp(power * (log(u) + log(sm))), 0 where u == 0        bias == 0
+ *          = bias^power * expm1(power * log1p(u * sm / bias))       otherwise
+ * s, a = 1.0 - s, log(eps) and bias^power are computed once on the host in float64.  Time is not cut into blocks: both kernels
+ * (SMX_DISABLE_FAST=1 forces the general one), a leading slice of a batch, a call continued from another call's zf and every
+ * chunking of the stream kernel give the same bits.  Negative or non-finite cells do not fault and are not otherwise specified.
+ *
+ *   smx_pcen_create      s = b when has_b; otherwise T = time_constant * sr / hop and s = (sqrt(1 + 4 T T) - 1) / (2 T T).
+ *                        Refused in words: gain < 0, bias < 0, power < 0, eps <= 0, time_constant <= 0, sr or hop <= 0,
+ *                        b outside [0, 1], scale <= 0, power == 0 together with bias == 0, any non-finite parameter.
+ *   smx_pcen_coefficient s.
+ *   smx_pcen_tile_min_frames  calls of at least this many frames (16) take the tile kernel, shorter ones the general kernel.
+ *   smx_pcen_apply_*     [rows; frames] -> [rows; frames]; zi: NULL or [rows] float64; zf: NULL or [rows] float64, M at the
+ *                        last frame.  frames = 0 hands zi back as zf (zero without one).
+ *   smx_pcen_smooth_*    the smoother alone: M rounded once to the dtype of S.
+ *   smx_pcen_of_audio_*  audio [lead; n] -> [lead; n_mels; frames]: smx_pcen_apply_* of smx_mel_spectrogram_* with power 1.0,
+ *                        bit for bit; the mel spectrogram lies in device scratch and never leaves the device.
+ *   smx_pcen_kernel_*    Pcen.Kernel.{prepare, step, flush, reset}: one double per row stays on the device (M at the last frame
+ *                        fed); whether the stream has started is a host flag.  A step takes [rows; m] and returns [rows; m]
+ *                        (latency zero); the first non-empty step takes M[-1] from its own first column.  The concatenated
+ *                        steps equal smx_pcen_apply_* of the whole spectrogram bit for bit.  flush emits nothing and drains the
+ *                        kernel: a step after it is refused until reset.  The first step allocates the state on its device;
+ *                        the state is input and output of every later step, so a kernel belongs to that device (another is
+ *                        refused in words) and to one stream at a time: steps on different streams are the caller's to order.
+ *
+ * The device-resident forms end in `_card_f32` and take the stream directly after the first argument (tables and laws of their
+ * own: tests/test_gpu_placement_pcen.py, tests/test_gpu_streams_pcen.py).  Rows of d_x lie x_stride >= frames (of_audio: >= n)
+ * elements apart and may start at any 4-byte position, results are dense; d_zi and d_zf are DEVICE arrays here and may be the
+ * same array.  Everything is enqueued on `stream`; nothing synchronises it. */
+typedef struct smx_pcen smx_pcen;
+typedef struct smx_pcen_kernel smx_pcen_kernel;
+int smx_pcen_create(int64_t sr, int64_t hop, double gain, double bias, double power, double time_constant, double eps, int has_b,
+                    double b, double scale, smx_pcen **out);
+void smx_pcen_destroy(smx_pcen *c);
+double smx_pcen_coefficient(const smx_pcen *c);
+int64_t smx_pcen_tile_min_frames(void);
+int smx_pcen_apply_f32(const smx_pcen *c, const float *x, int64_t rows, int64_t frames, const double *zi, float *out, double *zf);
+int smx_pcen_apply_f64(const smx_pcen *c, const double *x, int64_t rows, int64_t frames, const double *zi, double *out, double *zf);
+int smx_pcen_apply_card_f32(const smx_pcen *c, void *stream, const float *d_x, int64_t rows, int64_t frames, int64_t x_stride,
+                            const double *d_zi, float *d_out, double *d_zf);
+int smx_pcen_smooth_f32(const smx_pcen *c, const float *x, int64_t rows, int64_t frames, const double *zi, float *out);
+int smx_pcen_smooth_f64(const smx_pcen *c, const double *x, int64_t rows, int64_t frames, const double *zi, double *out);
+int smx_pcen_smooth_card_f32(const smx_pcen *c, void *stream, const float *d_x, int64_t rows, int64_t frames, int64_t x_stride,
+                             const double *d_zi, float *d_out);
+int smx_pcen_of_audio_f32(const smx_pcen *c, const smx_stft_config *sc, const smx_mel_config *mc, const float *x, int64_t lead,
+                          int64_t n, float *out);
+int smx_pcen_of_audio_f64(const smx_pcen *c, const smx_stft_config *sc, const smx_mel_config *mc, const double *x, int64_t lead,
+                          int64_t n, double *out);
+int smx_pcen_of_audio_card_f32(const smx_pcen *c, void *stream, const smx_stft_config *sc, const smx_mel_config *mc,
+                               const float *d_x, int64_t lead, int64_t n, int64_t x_stride, float *d_out);
+int smx_pcen_kernel_prepare(const smx_pcen *c, int64_t rows, smx_pcen_kernel **out);
+void smx_pcen_kernel_destroy(smx_pcen_kernel *k);
+int smx_pcen_kernel_reset(smx_pcen_kernel *k);
+int smx_pcen_kernel_flush(smx_pcen_kernel *k);
+int smx_pcen_kernel_step_f32(smx_pcen_kernel *k, const float *x, int64_t m, float *out);
+int smx_pcen_kernel_step_f64(smx_pcen_kernel *k, const double *x, int64_t m, double *out);
+int smx_pcen_kernel_step_card_f32(smx_pcen_kernel *k, void *stream, const float *d_x, int64_t m, int64_t x_stride, float *d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ module names:
     from soundml_amd import Decompose, nmf, nmf_activations, nmf_reconstruct, nmf_divergence
     from soundml_amd import Iir                       # Iir.Config.create(sos), Iir.apply, Iir.filtfilt, Iir.zi, Iir.Kernel
     from soundml_amd import Loudness, loudness, true_peak      # BS.1770: Loudness.integrated / momentary / short_term / normalize / Meter
+    from soundml_amd import Pcen, pcen                # per-channel energy normalisation: Pcen.Config.create, Pcen.apply / smooth / Kernel
     from soundml_amd import mel_to_stft, mel_to_audio, mfcc_to_mel, mfcc_to_audio      # and Mel.invert, Convert.db_to_power, ...
 
 Everything computes in hand-written HIP kernels (gfx950) behind the C ABI of
@@ -46,6 +47,8 @@ from .decompose import nmf, nmf_activations, nmf_reconstruct, nmf_divergence
 from . import iir as Iir
 from . import loudness as Loudness
 from .loudness import integrated as loudness, true_peak      # (the flat function takes the package attribute; the module is Loudness)
+from . import pcen as Pcen
+from .pcen import pcen      # (the flat function takes the package attribute; the module is Pcen)
 from . import hpss as Hpss
 from .hpss import hpss_masks, hpss_of_spectrogram, hpss_of_stft, hpss, harmonic, percussive
 from . import effects as Effects
@@ -94,5 +97,5 @@ def get_devices():
 
 
 __all__ = ["Stft", "Mel", "Chroma", "Cqt", "Convert", "Window", "Fir", "Resample", "resample", "Spec", "mel_spectrogram", "mfcc", "chroma_stft", "chroma_cqt", "power_to_db", "amplitude_to_db", "spectral_centroid",
-           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_contrast_of_spectrogram", "spectral_contrast_stage", "onset_strength", "onset_strength_stage", "rms", "rms_of_spectrogram", "rms_stage", "zero_crossing_rate", "zero_crossing_rate_stage", "Pitch", "yin", "yin_difference", "yin_stage", "pyin", "pyin_observation", "pyin_decode", "Rhythm", "tempogram", "tempo", "beat_track", "Sequence", "cost_matrix", "dtw", "dtw_distance", "Decompose", "nmf", "nmf_activations", "nmf_reconstruct", "nmf_divergence", "Iir", "Loudness", "loudness", "true_peak", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
+           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_contrast_of_spectrogram", "spectral_contrast_stage", "onset_strength", "onset_strength_stage", "rms", "rms_of_spectrogram", "rms_stage", "zero_crossing_rate", "zero_crossing_rate_stage", "Pitch", "yin", "yin_difference", "yin_stage", "pyin", "pyin_observation", "pyin_decode", "Rhythm", "tempogram", "tempo", "beat_track", "Sequence", "cost_matrix", "dtw", "dtw_distance", "Decompose", "nmf", "nmf_activations", "nmf_reconstruct", "nmf_divergence", "Iir", "Loudness", "loudness", "true_peak", "Pcen", "pcen", "Hpss", "hpss_masks", "hpss_of_spectrogram", "hpss_of_stft", "hpss", "harmonic", "percussive", "Effects", "phase_vocoder", "time_stretch", "pitch_shift", "semitones", "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio", "shard", "set_interior", "set_pinned_results", "pinned_empty", "set_scratch_retention", "device_count", "set_devices", "get_devices",
            "InvalidArgument", "Failure", "LIB_PATH"]

@@ -463,6 +463,26 @@ SIGNATURES = {
     "smx_loudness_meter_read_f32": (cint, [vp, cint, vp]),
     "smx_loudness_meter_read_f64": (cint, [vp, cint, vp]),
     "smx_loudness_meter_read_card_f32": (cint, [vp, vp, cint, vp]),
+    "smx_pcen_create": (cint, [i64, i64, f64, f64, f64, f64, f64, cint, f64, f64, C.POINTER(vp)]),
+    "smx_pcen_destroy": (None, [vp]),
+    "smx_pcen_coefficient": (f64, [vp]),
+    "smx_pcen_tile_min_frames": (i64, []),
+    "smx_pcen_apply_f32": (cint, [vp, vp, i64, i64, vp, vp, vp]),
+    "smx_pcen_apply_f64": (cint, [vp, vp, i64, i64, vp, vp, vp]),
+    "smx_pcen_apply_card_f32": (cint, [vp, vp, vp, i64, i64, i64, vp, vp, vp]),
+    "smx_pcen_smooth_f32": (cint, [vp, vp, i64, i64, vp, vp]),
+    "smx_pcen_smooth_f64": (cint, [vp, vp, i64, i64, vp, vp]),
+    "smx_pcen_smooth_card_f32": (cint, [vp, vp, vp, i64, i64, i64, vp, vp]),
+    "smx_pcen_of_audio_f32": (cint, [vp, vp, vp, vp, i64, i64, vp]),
+    "smx_pcen_of_audio_f64": (cint, [vp, vp, vp, vp, i64, i64, vp]),
+    "smx_pcen_of_audio_card_f32": (cint, [vp, vp, vp, vp, vp, i64, i64, i64, vp]),
+    "smx_pcen_kernel_prepare": (cint, [vp, i64, C.POINTER(vp)]),
+    "smx_pcen_kernel_destroy": (None, [vp]),
+    "smx_pcen_kernel_reset": (cint, [vp]),
+    "smx_pcen_kernel_flush": (cint, [vp]),
+    "smx_pcen_kernel_step_f32": (cint, [vp, vp, i64, vp]),
+    "smx_pcen_kernel_step_f64": (cint, [vp, vp, i64, vp]),
+    "smx_pcen_kernel_step_card_f32": (cint, [vp, vp, vp, i64, i64, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
